@@ -31,9 +31,23 @@ through ONE continuous-batching solve (NMFBatchSolver.run_stream: a fixed number
 replicate slots per K, each refilled with the next waiting replicate when its replicate
 converged), so the tail of one batch overlaps the next batch's first passes -- the rate of
 a multi-batch job (a K grid or several ledgers in one process).  With the default
-schedule, a single-K run at K <= 16 ALSO times that stream over the same replicates and
-reports it as ``config.stream_value`` (with ``config.stream_replicates``); ``value`` stays
-the per-batch rate.
+schedule, a ``--full`` single-K run at K <= 16 ALSO times that stream over the same
+replicates and reports it as ``config.stream_value`` (with ``config.stream_replicates``);
+``value`` stays the per-batch rate.
+
+A plain run does only what the headline figure needs: set-up, ``--warmup`` steps, the
+``--steps`` timed steps, the optional output dump, the JSON line.  ``--full`` adds the
+secondary measurements, each timed in a run of its own after the headline region: the
+continuous-batching rate above, the strong-scaling form of a multi-GPU weak run
+(``config.strong_value``) and the replayed collective term of a dp run
+(``config.collective_s_per_step``).  Without ``--full`` those fields are null / absent.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the LAST timed step returned to
+its caller (the NMFResult of that ledger batch: spectra ``W``, transposed usages ``HT``,
+``err``, ``n_iter``, ``converged``) as ``DIR/<name>.npy`` (float32 / float64; ranks > 0
+write ``<name>.rank<r>.npy``).  Inputs and ledger seeds are fixed by the arguments, so two
+builds run with the same arguments can be compared output for output.  Above 64 MB in all,
+the large arrays are cut to a fixed seeded sample of their elements.
 
 Run: ``python bench.py [--gpus N --steps K --warmup W --mode weak|strong|dp]``.  N > 1
 runs one process per GPU over RCCL (xGMI): either under ``torch.distributed.run`` (the
@@ -43,7 +57,8 @@ process (before any GPU call; never an exec) and exits with its return code.  Th
 line carries the world size and backend the process group actually reported
 (``config.rccl_world``, ``config.backend``).  A weak-scaling run with N > 1 also times the
 strong-scaling form of the same step -- ONE ``--n-iter`` ledger batch dealt round-robin
-over the ranks -- and reports it as ``config.strong_value`` (replicates/s, whole job).
+over the ranks -- under ``--full``, and reports it as ``config.strong_value`` (replicates/s,
+whole job).
 
 Reference: the multi-worker factorize is GNU parallel over ``--worker-index``
 (/root/reference/Extras/run_parallel.py:48-51) with the round-robin ``worker_filter``
@@ -115,6 +130,11 @@ def main() -> int:
                     help="(testing) every rank on GPU 0: gloo process group, device "
                          "collectives on the one-shot xGMI kernels, no cooperative solves -- "
                          "RCCL takes one rank per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (stream_value, strong_value, "
+                         "the dp collective replay); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's result arrays as DIR/<name>.npy")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -304,7 +324,8 @@ def main() -> int:
                        "host_stage_s": res.stats.get("stream_host_stage_s")}
     else:
         for i in range(args.warmup):
-            if i == args.warmup - 1 and comm is not None and hasattr(comm, "record"):
+            if (args.full and i == args.warmup - 1 and comm is not None
+                    and hasattr(comm, "record")):
                 comm.record = []      # the collectives of one whole step (dp mode)
             step(i)
             if comm is not None and getattr(comm, "record", None) is not None:
@@ -321,6 +342,9 @@ def main() -> int:
     elapsed = max_over_ranks(elapsed)
     ms_per_step = 1000.0 * elapsed / args.steps
     reps_per_sec = n_total * args.steps / elapsed
+    if args.dump_outputs:
+        n_last = len(all_seeds[:n_total][rank::world]) if args.mode != "dp" else n_total
+        _dump_outputs(args.dump_outputs, res, n_last if stream else None, rank)
 
     # the multi-batch rate of the same replicates (continuous batching), beside the per-batch
     # value: timed separately, after the headline region
@@ -330,8 +354,8 @@ def main() -> int:
     if coll_calls:
         coll_s = comm.replay(coll_calls, reps=5)
     stream_value = stream_reps = None
-    if (not stream and stream_ok and len(grid) == 1 and args.schedule == "batch"
-            and not args.no_stream_value and use_cuda):
+    if (args.full and not stream and stream_ok and len(grid) == 1
+            and args.schedule == "batch" and not args.no_stream_value and use_cuda):
         if args.warmup:
             stream_steps(0, args.warmup)
         barrier()
@@ -345,7 +369,7 @@ def main() -> int:
         stream_value = stream_reps / el_st
 
     strong_value = strong_ms = None
-    if world > 1 and args.mode == "weak":
+    if args.full and world > 1 and args.mode == "weak":
         # the same ledger batch per step, now split over the ranks (strong scaling)
         if stream:
             stream_steps(0, min(2, args.warmup), strong=True) if args.warmup else None
@@ -399,6 +423,7 @@ def main() -> int:
                 "n_iter_per_gpu": args.n_iter,
                 "parallelism": par,
                 "scaling_mode": args.mode,
+                "full": args.full,
                 "streams_per_gpu": args.streams,
                 "schedule": ("continuous batching over the timed steps (run_stream): "
                              f"live slots per K {stream_info['slots']}, "
@@ -442,6 +467,43 @@ def main() -> int:
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def _dump_outputs(out_dir: str, res, n_last, rank: int) -> None:
+    """Write the arrays of ``res`` (an NMFResult) as ``out_dir/<name>.npy``.  ``n_last``: keep
+    only the last ``n_last`` replicates (the stream schedule solves every timed step in one
+    result; its last step's replicates are the tail)."""
+    import torch
+
+    R = len(res.seeds)
+    lo = 0 if n_last is None else max(0, R - int(n_last))
+    row0 = int(res.offs[lo]) if R else 0
+    arrays = {}
+    for name in ("W", "HT"):
+        t = getattr(res, name, None)
+        if isinstance(t, torch.Tensor) and t.numel():
+            a = t.detach().cpu().numpy()[row0:]
+            arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    for name in ("err", "n_iter", "converged"):
+        arrays[name] = np.asarray(getattr(res, name))[lo:].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        # a fixed seeded sample of the large arrays' elements, sized to fit the budget
+        small = sum(a.nbytes for a in arrays.values() if a.nbytes <= (1 << 20))
+        big = total - small
+        frac = (0.95 * DUMP_BYTES_MAX - small) / big
+        rng = np.random.default_rng(0)
+        for name, a in arrays.items():
+            if a.nbytes > (1 << 20):
+                idx = np.sort(rng.choice(a.size, size=int(a.size * frac), replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        fn = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(out_dir, fn), np.ascontiguousarray(a))
 
 
 def _free_port() -> int:

@@ -82,7 +82,7 @@ def test_bench_self_launches_n_ranks_without_a_launcher():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + tiny, cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full"] + tiny, cwd=ROOT,
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -93,6 +93,35 @@ def test_bench_self_launches_n_ranks_without_a_launcher():
     # weak run also reports the strong form: one 3-replicate batch per step over 2 ranks
     assert out["config"]["strong_global_batch"] == 3
     assert out["config"]["strong_value"] > 0
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the secondary measurements do not run (their fields are null);
+    ``--dump-outputs`` writes the last timed step's result arrays, identical from run to
+    run with the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        out = _bench(["--dump-outputs", str(d)], 1)
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert out["config"]["full"] is False
+        assert out["config"]["stream_value"] is None
+        assert out["config"]["strong_value"] is None
+        assert "collective_s_per_step" not in out["config"]
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    a, b = dumps
+    assert {"W.npy", "err.npy", "n_iter.npy", "converged.npy"} <= set(a) and set(a) == set(b)
+    assert a["W.npy"].shape == (3 * 4, 60) and a["W.npy"].dtype == np.float32
+    assert a["err.npy"].shape == (3,) and a["n_iter.npy"].shape == (3,)
+    assert np.all(np.isfinite(a["W.npy"])) and np.all(a["W.npy"] >= 0)
+    total = 0
+    for key in a:
+        assert a[key].dtype in (np.float32, np.float64), key
+        assert np.array_equal(a[key], b[key]), key
+        total += a[key].nbytes
+    assert total <= 64 * 1000 * 1000
 
 
 def test_bench_world_size_mismatch_fails():
@@ -110,7 +139,7 @@ def test_bench_eight_ranks_weak_strong_dp():
     strong (ONE 3-replicate ledger batch over 8 ranks: five ranks own nothing) and dp
     (300 cells in 100-cell chunks over 8 ranks: 12-13 cells per rank and chunk) all
     complete and print one whole-job JSON line; weak reports its strong form too."""
-    weak = _bench([], 8)
+    weak = _bench(["--full"], 8)
     assert weak["n_gpus"] == 8 and weak["config"]["rccl_world"] == 8
     assert weak["config"]["global_batch"] == 24 and weak["scaling"] == "weak"
     assert weak["config"]["strong_value"] > 0 and weak["config"]["strong_global_batch"] == 3

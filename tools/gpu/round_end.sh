@@ -2,7 +2,7 @@
 # steps, KL / K-grid benches, five e2e pipeline runs, a kernel trace of the headline.
 # usage: bash tools/gpu/round_end.sh <tag>   (logs under gpurun_out/<tag>)
 exec bash "$(dirname "$0")/run.sh" "$1" pytest smoke \
-  'bench|150|python bench.py --steps 20 --warmup 5' \
+  'bench|150|python bench.py --steps 20 --warmup 5 --full' \
   'bench40|150|python bench.py --steps 40 --warmup 5 --no-stream-value' \
   'bench_kl|300|python bench.py --beta-loss kullback-leibler --steps 3 --warmup 1' \
   'grid|150|python bench.py --kmin 5 --kmax 13 --steps 5 --warmup 2' \
