@@ -595,8 +595,9 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
         G = self.X.shape[1]
         cws = [b - a for (a, b), in steps]
         bk = ops.planes_bk(xp.pb)
-        ks_n = max(ops.gemm_plan(rows, cw, xp.Gp, xp.pb)[1] for cw in cws)
-        ks_b = max(ops.gemm_plan(rows, G, -(-cw // bk) * bk, xp.pb)[1] for cw in cws)
+        ks_n = max(ops.gemm_plan(rows, cw, xp.Gp, xp.pb, _FUSED_MAX_SLABS)[1] for cw in cws)
+        ks_b = max(ops.gemm_plan(rows, G, -(-cw // bk) * bk, xp.pb, _FUSED_MAX_SLABS)[1]
+                   for cw in cws)
         S = ops.kCoopMaxSlices
         ngp = sum(g.n * S * g.K * g.K for g in st.groups)
         kd_max = max(-(-cw // bk) * bk for cw in cws)

@@ -47,7 +47,7 @@ class _DPMixin:
         cws = [b - a for (a, b), in steps]
         units = _dp_units(st.groups, self.comm.world_size)
         # the numerator slab of the widest unit's GEMM plan (a half's split can be deeper)
-        slab = max(ops.gemm_plan(g.n * g.K, cw, xp.Gp, xp.pb)[1] * g.n * g.K * cw
+        slab = max(ops.gemm_plan(g.n * g.K, cw, xp.Gp, xp.pb, _FUSED_MAX_SLABS)[1] * g.n * g.K * cw
                    for cw in cws for g in units)
         f32 = dict(device=dev, dtype=torch.float32)
         groups = [self._fused_bufs_dp_group(g, steps) for g in units]

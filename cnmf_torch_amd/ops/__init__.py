@@ -12,6 +12,7 @@ kernel is never handed an operand layout it does not assume.
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 import threading
 from typing import NamedTuple
@@ -1973,14 +1974,24 @@ def gemm_kstep(variant: int) -> int:
     a multiple of 64).  Measured on MI355X (profiles/r2_gemm_bk_sweep.txt): the 8-wave
     128x256 tiles gain (K=10 statistics GEMM 62 -> 60 us, K-grid GEMMs 410/393 -> 400/381 us,
     as 2 stages of 64 against 3 of 32), the 2- and 4-wave tiles lose (64x128 numerator
-    77 -> 97 us).  CNMF_GEMM_BK overrides (A/B runs)."""
+    77 -> 97 us); the NI != 4 tiles (ids 6-9) run 64 deep, see _GEMM_DEEP.  CNMF_GEMM_BK
+    overrides (A/B runs)."""
     if _ENV["CNMF_GEMM_BK"]:
         return int(_ENV["CNMF_GEMM_BK"])
-    return 64 if variant in (1, 2, 5) else 32
+    return 64 if variant in _GEMM_DEEP else 32
 
 
+# (M-tile, N-tile) per variant: 0-5 are wave blocks of four 16-column blocks; 6 / 7 of five
+# (128 x 160 as 4 waves, 128 x 320 as 8 waves: 256 tiles for a 1000 / 2000 x 5000 output);
+# 8 / 9 of two / one (narrow tiles for the few-row tail layouts)
 _GEMM_TILES = {0: (128, 128), 1: (128, 256), 2: (256, 128), 3: (64, 128), 4: (64, 128),
-               5: (128, 128)}
+               5: (128, 128), 6: (128, 160), 7: (128, 320), 8: (128, 64), 9: (128, 32)}
+# variants run with the 64-deep k-step / with a third LDS stage.  6-9 in
+# profiles/p1_gemm_tile_family_sweep.log: two 64-deep stages were the best or within 3 % of
+# it wherever the variant was near a shape's best (128 x 160 at the 1000 x 5000 numerator:
+# 43.2 us, three stages 45.2, 32 deep 48.1 / 51.5)
+_GEMM_DEEP = (1, 2, 5, 6, 7, 8, 9)
+_GEMM_THREE_STAGES = (1, 2, 5)
 _GEMM_SLAB: dict = {}
 
 
@@ -1993,10 +2004,54 @@ def gemm_a_planes(Kd: int) -> int:
     return 3 if Kd < 1024 else 2
 
 
-def gemm_plan(M: int, N: int, Kd: int, pb: int) -> tuple[int, int]:
-    """(tile variant, k split) for an M x N x Kd split GEMM: the largest tile that still
-    gives every CU a workgroup, else k-split slices (deterministic slab reduction) until
-    ~2 workgroups per CU.  CNMF_GEMM_VARIANT / CNMF_GEMM_KSPLIT override (benchmarks)."""
+# Cost model of gemm_plan, per variant: (fixed us per workgroup, us per 64-deep k-step of a
+# workgroup that has its CU to itself, us per k-step and workgroup-per-CU of several
+# co-resident workgroups; 0 = the tile runs one workgroup per CU, in whole waves of
+# workgroups).  Fitted (least absolute relative error, the configurations within 1.3x of
+# a shape's best weighted 1, the others 0.15) to profiles/p1_gemm_tile_family_sweep.log:
+# two A planes, one B plane, N x Kd = 5000 x 2048 and 2000 x 5056, M = 20 ... 3000, raw
+# slabs (ids 6, 8, 9: their b64s2 entries).  Weighted mean / worst error per variant:
+# 0 6 / 28 %, 1 5 / 19 %, 2 5 / 22 %,
+# 5 6 / 30 %, 6 5 / 20 %, 7 5 / 23 %, 8 6 / 23 %, 9 5 / 32 %.  The 64-row tiles 3 and 4
+# are no candidates: among the swept shapes they won only the 20-row numerator (8.2 us
+# against 10.7), and their fit was the worst (11 / 37 %), which cost more where it
+# mis-ranked them (320-row statistics: 29.9 us picked against 23.1).
+_GEMM_COST = {0: (4.0, 1.15, 1.00), 1: (3.0, 1.40, 0.0), 2: (2.0, 1.55, 0.0),
+              5: (1.5, 0.95, 0.0), 6: (2.0, 1.20, 0.0), 7: (4.0, 1.65, 0.0),
+              8: (3.5, 0.65, 0.55), 9: (3.0, 0.60, 0.40)}
+# us per MB of each slab after the first: 0.25 to write it (the value the fit above was made
+# with) + 0.25 for the consumer to read it (4 TB/s, about the HBM rate: reasoned, not fitted)
+_GEMM_SLAB_US_PER_MB = 0.5
+# a k split of more slices than the consumer takes raw (models.nmf_base._FUSED_MAX_SLABS
+# for the fused pass) is reduced by a gemm_reduce launch: its launch on the pass's
+# dependency chain (7.3 us a call in profiles/r6c_swapcompact_passes.txt) and a read of
+# every slab
+_GEMM_REDUCE_US = 7.0
+_GEMM_KSPLITS = (1, 2, 3, 4, 6, 8, 12, 16)
+
+
+def _gemm_cost(v: int, ks: int, M: int, N: int, nk: int, pairs: int, raw_max: int) -> float:
+    tm, tn = _GEMM_TILES[v]
+    fixed, c_alone, c_shared = _GEMM_COST.get(v, _GEMM_COST[0])
+    load = -(-M // tm) * -(-N // tn) * ks / 256.0       # workgroups per CU
+    steps = -(-nk // ks) * pairs / 2.0      # k-steps per workgroup, in units of the fit's
+    if c_shared == 0.0:                     # two plane pairs (MFMAs per k-step ~ pairs)
+        cost = math.ceil(load) * (fixed + steps * c_alone)
+    else:
+        cost = fixed + steps * max(c_alone, c_shared * load)
+    mb = M * N * 4e-6
+    cost += _GEMM_SLAB_US_PER_MB * (ks - 1) * mb
+    if ks > raw_max:
+        cost += _GEMM_REDUCE_US + 0.25 * mb
+    return cost
+
+
+def _gemm_plan_reduced(M: int, N: int, Kd: int, pb: int) -> tuple[int, int]:
+    """gemm_plan for a product whose k split is summed by a gemm_reduce launch (no raw
+    slabs): the largest tile that still gives every CU a workgroup, else k-split slices
+    (deterministic slab reduction) until ~2 workgroups per CU.  These rules were measured
+    with the reduction pass in the time and use tile variants 0-5 only; the NI != 4 tiles
+    have not been measured on this path."""
     cus = 256
     nk = Kd // planes_bk(pb)
     v_env, k_env = _ENV["CNMF_GEMM_VARIANT"], _ENV["CNMF_GEMM_KSPLIT"]
@@ -2049,6 +2104,48 @@ def gemm_plan(M: int, N: int, Kd: int, pb: int) -> tuple[int, int]:
         while t * ksplit < target and nk // (2 * ksplit) >= 4:
             ksplit *= 2
     return v, max(1, min(ksplit, nk))
+
+
+def gemm_plan(M: int, N: int, Kd: int, pb: int, raw_max: int | None = None) -> tuple[int, int]:
+    """(tile variant, k split) for an M x N x Kd split GEMM.  ``raw_max`` None: the product
+    is reduced by the GEMM itself (``_gemm_plan_reduced``, the rules measured with the
+    reduction pass).  ``raw_max`` = the number of raw slabs the consumer sums (the fused
+    online pass, ``gemm_planes(raw_slab=...)``): the cheapest pair under ``_gemm_cost`` --
+    waves of workgroups over the 256 CUs times the k length of a workgroup, plus the
+    traffic of every slab beyond the first -- so a tile that covers the output in one wave
+    without a k split (128 x 160 for 1000 x 5000, 128 x 320 for 2000 x 5000) beats both
+    smaller tiles and a split.  Every k slice keeps >= 4 k-steps.
+    CNMF_GEMM_VARIANT / CNMF_GEMM_KSPLIT fix either or both (benchmarks, tests)."""
+    if raw_max is None:
+        return _gemm_plan_reduced(M, N, Kd, pb)
+    nk = Kd // planes_bk(pb)
+    v_env, k_env = _ENV["CNMF_GEMM_VARIANT"], _ENV["CNMF_GEMM_KSPLIT"]
+    if v_env is not None and k_env is not None:
+        return int(v_env), max(1, min(int(k_env), nk))
+    pa = gemm_a_planes(Kd)
+    pairs = sum(1 for i in range(pa) for j in range(pb) if i + j <= 2)
+    # (128 x 320 with 3 + 3 planes does not fit in LDS even 32 deep, and a caller may pass
+    # three A planes whatever Kd: never planned with three B planes; a variant fixed by the
+    # environment that the model has no constants for is costed as the 128 x 128 tile)
+    variants = [int(v_env)] if v_env is not None else \
+        [v for v in _GEMM_COST if not (v == 7 and pb == 3)]
+    # beyond 4096 rows (several waves of workgroups; the fit has no shape that large): only
+    # the two 8-wave one-per-CU tiles, which led every swept shape from 2000 rows up (at
+    # 5000 rows: numerator 128 x 320 188 us, 128 x 256 202; statistics 264 against 221, as
+    # the whole-wave count says), and no k split: at K = 50 the slabs cost the solves more
+    # than the GEMMs gained (1,300 -> 1,211 rep/s, profiles/r4r_*)
+    big = M > 4096
+    if big and v_env is None:
+        variants = [v for v in variants if v in (1, 7)]
+    splits = [max(1, min(int(k_env), nk))] if k_env is not None else \
+        [ks for ks in _GEMM_KSPLITS if ks == 1 or (nk // ks >= 4 and not big)]
+    best = None
+    for v in variants:
+        for ks in splits:
+            cost = _gemm_cost(v, ks, M, N, nk, pairs, raw_max)
+            if best is None or cost < best[0] - 1e-9:
+                best = (cost, v, ks)
+    return best[1], best[2]
 
 
 def split_planes(S: torch.Tensor, out: torch.Tensor, col_mul: torch.Tensor | None = None) -> None:
@@ -2136,7 +2233,8 @@ def gemm_planes(C: torch.Tensor | None, A: torch.Tensor, B: torch.Tensor, M: int
         else:
             C[:M, :N] = prod.to(C.dtype)
         return
-    variant, ksplit = plan if plan is not None else gemm_plan(M, N, Kd, pb)
+    variant, ksplit = plan if plan is not None else gemm_plan(
+        M, N, Kd, pb, raw_max if raw_slab is not None else None)
     slab = 0
     if raw_slab is not None and ksplit > raw_max:
         # (capping ksplit at raw_max instead -- no reduction pass, fewer workgroups -- was
@@ -2174,10 +2272,12 @@ def gemm_stages(variant: int) -> int:
     (profiles/r2_gemm_stages_sweep.txt): the 8-wave tiles (128x256, 256x128; one
     workgroup per CU) gain from a third stage (stats GEMM of the K-grid 442 -> 407 us),
     the 2- and 4-wave tiles lose more occupancy than they gain latency cover (64x128
-    numerator 80 -> 108 us).  CNMF_GEMM_STAGES overrides (A/B runs)."""
+    numerator 80 -> 108 us), and so do the 4-wave tiles of ids 6, 8, 9 (128 x 160 numerator
+    43.2 -> 45.2 us; 128 x 320 never fits three 64-deep stages).  CNMF_GEMM_STAGES overrides
+    (A/B runs)."""
     if _ENV["CNMF_GEMM_STAGES"]:
         return int(_ENV["CNMF_GEMM_STAGES"])
-    return 3 if variant in (1, 2, 5) else 2
+    return 3 if variant in _GEMM_THREE_STAGES else 2
 
 
 # ----------------------------------------------------------------------------- column stats
