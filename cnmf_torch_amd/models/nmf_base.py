@@ -70,6 +70,12 @@ class NMFOptions:
     # r4c_kl_*; CSR vs dense rep/s): 8 % 564 / 381, 15 % 403 / 365, 25 % 290 / 348,
     # 35 % 228 / 338 -- equal near 19 %; at the headline's 47 % the dense kernels win
     kl_sparse_density: float = 0.18
+    # the same threshold for 32 < K <= 64 (sparse_kl_wide.hip).  Measured
+    # (profiles/p2_kl_wide_ab.txt; CSR vs dense rep/s): K = 48: 8 % 98 / 64, 15 % 60 / 62,
+    # 25 % 39 / 62; K = 64: 8 % 69 / 57, 15 % 44 / 55, 25 % 29 / 55 -- the time per
+    # replicate is linear in the density on the CSR side and flat on the dense one, equal
+    # near 14 % (K = 48) and 10.7 % (K = 64); one threshold below both
+    kl_sparse_density_wide: float = 0.10
 
     @classmethod
     def from_kwargs(cls, n_components: int, **kw) -> "NMFOptions":

@@ -61,25 +61,34 @@ class _BetaMixin:
 
     def _kl_sparse(self):
         """CSR of X (ops.KLCSR) when the KL MU statistics run on the sparse kernels
-        (sparse_kl.hip): KL on the native GPU path with X at most ``kl_sparse_density``
-        non-zero (``CNMF_KL_SPARSE=1`` forces it, ``=0`` disables it); else None (dense
-        split-precision kernels).  Decided once per solver (one host sync)."""
-        if getattr(self, "_beta_K", 0) > 32:     # the CSR kernels stop at K = 32
+        (sparse_kl.hip, sparse_kl_wide.hip above K = 32): KL on the native GPU path at
+        K <= 64 with X at most ``kl_sparse_density`` non-zero (``kl_sparse_density_wide``
+        for 32 < K <= 64; ``CNMF_KL_SPARSE=1`` forces it, ``=0`` disables it); else None
+        (dense split-precision kernels).  The density is read once per solver (one host
+        sync), the route decided once per rank."""
+        K = max(getattr(self, "_beta_K", 0), self.opts.n_components)
+        if K > 64:                               # the CSR kernels stop at K = 64
             return None
-        if "_kl_csr" in self.__dict__:
-            return self._kl_csr
-        csr = None
-        X = self.X
-        env = os.environ.get("CNMF_KL_SPARSE", "")
-        if (self.beta == 1.0 and env != "0" and isinstance(X, torch.Tensor)
-                and X.device.type == "cuda" and X.dtype == torch.float32
-                and self.opts.n_components <= 32 and ops.use_native(X)):
-            dens = float((X != 0).sum()) / max(X.numel(), 1)
-            if env == "1" or dens <= float(self.opts.kl_sparse_density):
-                csr = ops.kl_csr(X)
-        self._kl_csr = csr
-        self._kl_csrT = {}
-        return csr
+        if "_kl_route" not in self.__dict__:
+            X = self.X
+            self._kl_route = {}
+            self._kl_csr = None
+            self._kl_csrT = {}
+            self._kl_dens = None                 # None: not eligible at any rank
+            if (self.beta == 1.0 and isinstance(X, torch.Tensor) and X.device.type == "cuda"
+                    and X.dtype == torch.float32 and ops.use_native(X)):
+                self._kl_dens = float((X != 0).sum()) / max(X.numel(), 1)
+        wide = K > 32
+        if wide not in self._kl_route:
+            env = os.environ.get("CNMF_KL_SPARSE", "")
+            cap = self.opts.kl_sparse_density_wide if wide else self.opts.kl_sparse_density
+            self._kl_route[wide] = (self._kl_dens is not None and env != "0"
+                                    and (env == "1" or self._kl_dens <= float(cap)))
+        if not self._kl_route[wide]:
+            return None
+        if self._kl_csr is None:
+            self._kl_csr = ops.kl_csr(self.X)
+        return self._kl_csr
 
     def _kl_counts(self):
         """(xh (N, G) float16, xth (G, N) float16, unit (G,), 1 / unit (G,)) when the dense
@@ -90,13 +99,14 @@ class _BetaMixin:
         sparse path.  Only the spectra side reads the fp16 counts, the usage side fp32 X
         -- on the usage side the fp16 -> fp32 conversion costs more issue than the halved
         bytes save (326-329 vs 314-317 rep/s with both sides, profiles/r3v_*, r3w_*)."""
+        if self._kl_sparse() is not None:      # per rank: not part of the cached answer
+            return None
         if "_klc" in self.__dict__:
             return self._klc
         res = None
         X = self.X
         if (self.beta == 1.0 and isinstance(X, torch.Tensor) and X.device.type == "cuda"
-                and X.dtype == torch.float32 and ops.use_native(X)
-                and self._kl_sparse() is None):
+                and X.dtype == torch.float32 and ops.use_native(X)):
             unit = _count_units(X, self._colstats)
             if unit is not None:
                 unit = unit.to(device=X.device, dtype=torch.float32).contiguous()
@@ -114,9 +124,10 @@ class _BetaMixin:
 
     def _kl_rows_T(self, a: int, b: int):
         """Tiled CSRs of X[a:b]^T (genes x chunk cells) for the sparse spectra numerators."""
-        key = (a, b)
+        K = self._beta_K or self.opts.n_components
+        key = (a, b, ops.kl_tile_rows(K))
         if key not in self._kl_csrT:
-            self._kl_csrT[key] = ops.kl_csr_tiles(self.X[a:b], self._beta_K or self.opts.n_components)
+            self._kl_csrT[key] = ops.kl_csr_tiles(self.X[a:b], K)
         return self._kl_csrT[key]
 
     def _beta_w_partials(self, xc, xtc, H3c, W3, active, panels=None, rows=None):

@@ -1329,7 +1329,8 @@ def beta_w_partials(X: torch.Tensor, XT: torch.Tensor | None, HT3: torch.Tensor,
 
 # ------------------------------------------------------------- sparse KL (CSR X)
 class KLCSR(NamedTuple):
-    """CSR of a non-negative matrix for the sparse KL kernels (sparse_kl.hip): row i owns
+    """CSR of a non-negative matrix for the sparse KL kernels (sparse_kl.hip, K <= 32;
+    sparse_kl_wide.hip, 33 <= K <= 64): row i owns
     entries [rowptr[i], rowptr[i+1]) of col / val; a row range is a rowptr slice over the
     same col / val (:func:`kl_csr_rows`)."""
     rowptr: torch.Tensor    # int32 (n_rows + 1,), absolute offsets
@@ -1384,7 +1385,7 @@ def _sk_args(csr: KLCSR, F3: torch.Tensor, S3: torch.Tensor, st: torch.Tensor | 
     if csr.n_rows != Lf or csr.n_cols != Ls or csr.rowptr.dtype != torch.int32:
         raise ValueError(f"CSR {csr.n_rows} x {csr.n_cols} does not match fixed {Lf} x "
                          f"streamed {Ls}")
-    _native_dtype_k("sparse KL", F3.dtype, K, 32)
+    _native_dtype_k("sparse KL", F3.dtype, K, 64)
     for name, t in (("F3", F3), ("S3", S3)):
         _bp_check(name, t, F3.device)
     if st is None:

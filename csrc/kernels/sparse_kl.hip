@@ -18,51 +18,15 @@
 // panel, so the usage side runs all `nsteps` MU steps of a column back to back with the
 // usages in registers.  The block-objective stopping rule is the dense kernel's (last
 // workgroup of the replicate to arrive decides, cdna_hip_programming.md G16).
+//
+// This unit holds the K <= 32 kernel and the launcher for every K <= 64; 33 <= K <= 64 run
+// sparse_kl_wide.hip (components split over the lanes of a row), sparse_kl.h is shared.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "sparse_kl.h"
 
 namespace cnmf {
-
-typedef float sk_f2 __attribute__((ext_vector_type(2)));
-
-constexpr int kSkThreads = 256;                 // global-gather variant
-constexpr int kSkThreadsL = 512;                // LDS variant (one workgroup per CU)
-constexpr int kSkRow = 16;                      // lanes per fixed column (one DPP row)
-constexpr int kSkCols = kSkThreads / kSkRow;    // columns in flight per workgroup
-constexpr int kSkLdsBytes = 128 * 1024;         // LDS budget for the staged S^T rows
-
-struct SkParams {
-  const int* rowptr;   // (Lf + 1): fixed column i owns entries [rowptr[i], rowptr[i+1])
-  const int* col;      // streamed index of each entry
-  const float* val;    // x of each entry
-  const float* ST;     // streamed operand, transposed: replicate r, row l at ST + r*st_rs + l*K4
-  long long st_rs;
-  float* F;            // fixed operand (R, K, Lf): F + r*f_rs + k*ldf + i
-  long long f_rs, ldf;
-  int K, K4, Lf, Ls, R;
-  int cols_per_wg, n_groups;
-  float eps;
-  float* num;          // side W: (R, K, Lf)
-  int nsteps, loss_entry, loss_exit;
-  const float* den_vec;  // (R, K) row sums of S
-  float l1, l2, tol;
-  int conv_mode;
-  double* hstate;      // (R, 2)
-  double* part;        // (R, n_groups, 4)
-  int* counter;        // (R)
-  int* act;            // (R)
-  int* iters;          // (R)
-  const int* active;   // (R) gate
-  double* loss;        // loss-only launches: (R, n_groups)
-  double xsum;
-};
-
-template <int CTRL>
-__device__ __forceinline__ float sk_dpp(float v) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 
 // sum over the 16 lanes of a DPP row; every lane of the row receives it
 __device__ __forceinline__ float sk_row_sum(float v) {
@@ -93,7 +57,7 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
   const int grp = local / RX;
   if (rep >= p.R || grp >= p.n_groups) return;
   if (p.active && p.active[rep] == 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int rl = tid & (kSkRow - 1), rc = tid / kSkRow;
   const int K = p.K;
   const float* __restrict__ ST = p.ST + (long long)rep * p.st_rs;
@@ -235,63 +199,7 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
   }
   if (!UPD) return;
 
-  // workgroup partials -> the replicate's stopping rule (as beta_planes.hip bp_kernel)
-  {
-    const double v0 = wave_sum((double)d2), v1 = wave_sum((double)o2);
-    const double v2 = wave_sum(f_entry), v3 = wave_sum(f_exit);
-    if (lane == 0) {
-      sred[wave * 4 + 0] = v0;
-      sred[wave * 4 + 1] = v1;
-      sred[wave * 4 + 2] = v2;
-      sred[wave * 4 + 3] = v3;
-    }
-    __syncthreads();
-  }
-  constexpr int kW = NTH / 64;
-  if (p.loss && tid == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < kW; ++w) tot += sred[w * 4 + 3];
-    p.loss[(long long)rep * p.n_groups + grp] = tot;
-  }
-  if (!p.part) return;
-  if (tid == 0) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int w = 0; w < kW; ++w)
-      for (int v = 0; v < 4; ++v) acc[v] += sred[w * 4 + v];
-    double* pp = p.part + ((long long)rep * p.n_groups + grp) * 4;
-    for (int v = 0; v < 4; ++v) pp[v] = acc[v];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int prev = __hip_atomic_fetch_add(p.counter + rep, 1, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (prev == p.n_groups - 1);
-  }
-  __syncthreads();
-  if (s_last && tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    double tot[4] = {0.0, 0.0, 0.0, 0.0};
-    const double* pr = p.part + (long long)rep * p.n_groups * 4;
-    for (int g2 = 0; g2 < p.n_groups; ++g2)
-      for (int v = 0; v < 4; ++v)
-        tot[v] += __hip_atomic_load(pr + 4 * g2 + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot[2] -= p.xsum;
-    tot[3] -= p.xsum;
-    if (p.conv_mode == 1) {
-      double* hs = p.hstate + 2 * (long long)rep;
-      const double f_prev = p.loss_entry ? tot[2] : hs[0];
-      if ((p.loss_entry || hs[1] > 0.0) && fabs(f_prev - tot[3]) <= (double)p.tol * fabs(f_prev))
-        p.act[rep] = 0;
-      hs[0] = tot[3];
-      hs[1] = hs[1] + 1.0;
-    } else if (p.nsteps > 0) {
-      const double rel = sqrt(tot[0]) / (sqrt(tot[1]) + (double)p.eps);
-      if (rel < (double)p.tol) p.act[rep] = 0;
-    }
-    if (p.iters) p.iters[rep] += p.nsteps;
-    p.counter[rep] = 0;
-  }
+  sk_tail<NTH>(p, rep, grp, d2, o2, f_entry, f_exit, sred, &s_last);
 }
 
 template <int NQ, bool UPD, bool LDS>
@@ -369,8 +277,8 @@ extern "C" hipError_t cnmf_sk_run(
     float l2, float tol, int conv_mode, double* hstate, double* part, int* counter, int* act,
     int* iters, const int* active, double* loss, double xsum, hipStream_t stream) {
   if (R <= 0 || Lf <= 0) return hipSuccess;
-  if (K < 1 || K > 32 || (side != 0 && side != 1) || rowptr == nullptr || ST == nullptr ||
-      (reinterpret_cast<uintptr_t>(ST) & 15) != 0 || st_rs % 4 != 0)
+  if (K < 1 || K > cnmf::kSkWideMaxK || (side != 0 && side != 1) || rowptr == nullptr ||
+      ST == nullptr || (reinterpret_cast<uintptr_t>(ST) & 15) != 0 || st_rs % 4 != 0)
     return hipErrorInvalidValue;
   cnmf::SkParams p;
   p.rowptr = rowptr; p.col = col; p.val = val;
@@ -385,15 +293,16 @@ extern "C" hipError_t cnmf_sk_run(
   p.den_vec = den_vec; p.l1 = l1; p.l2 = l2; p.tol = tol; p.conv_mode = conv_mode;
   p.hstate = hstate; p.part = part; p.counter = counter; p.act = act; p.iters = iters;
   p.active = active; p.loss = loss; p.xsum = xsum;
+  const bool wide = K > cnmf::kSkMaxK;   // sparse_kl_wide.hip: components split over lanes
   if (side == 1) {
     if (num == nullptr) return hipErrorInvalidValue;
-    return cnmf::sk_launch_u<false>(p, stream);
+    return wide ? cnmf::sk_wide_run(1, p, stream) : cnmf::sk_launch_u<false>(p, stream);
   }
   if (nsteps < 0 || den_vec == nullptr || (part != nullptr && (counter == nullptr || act == nullptr)) ||
       (part != nullptr && conv_mode == 1 && hstate == nullptr) ||
       (nsteps == 0 && loss == nullptr && part == nullptr))
     return hipErrorInvalidValue;
-  return cnmf::sk_launch_u<true>(p, stream);
+  return wide ? cnmf::sk_wide_run(0, p, stream) : cnmf::sk_launch_u<true>(p, stream);
 }
 
 extern "C" int cnmf_sk_groups(int Lf, int R, int Ls, int K) {
