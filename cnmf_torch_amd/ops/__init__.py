@@ -163,16 +163,15 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
     converging as a unit (cross-workgroup deterministic reductions, see coop_sum2 in
     solve.hip); "auto" picks S so that all S*nblocks workgroups are co-resident on the
     256 CUs, 1 disables.  Results are independent of S up to fp32 summation order.
-    ``variant``: "auto" runs MU with K <= 16 on the matrix-core kernel (solve_mfma.hip:
-    Gram x on v_mfma_f32_16x16x4_f32, iterate in VGPRs) whenever its slices fit, else
-    the VALU kernels ("stream" / "reg" force those; "mfma" forces the former).
+    ``variant``: "auto" takes the fastest kernel that covers the solve; "stream" / "reg"
+    force the streaming / register-resident VALU kernels (K > 64: "stream" the fp32 Gram
+    apply), "mfma" a matrix-core MU kernel or an error.  :func:`solve_plan` names the
+    kernel a call runs; docs/ARCHITECTURE.md ("Solve dispatch") has the rules.
     ``planes`` (>= planes_n, R*K, cols_pad) int16, optional: the kernel's epilogue also writes the
     final x (times ``planes_colmul`` per column) as exact bf16 planes -- the A operand of
     the next split-precision GEMM (ops.gemm_planes) -- zeroing columns [n, cols_pad).
     ``planes_n``: how many of the three planes to write (the GEMM reads only its
     ``gemm_a_planes(Kd)`` A planes; the rest would be dead stores).
-    MU with l1 = l2 = 0, the block-objective stop and K <= 16 runs the software-pipelined
-    matrix-core kernel (solve_pipe.hip) unless ``CNMF_SOLVE_PIPE=0``.
 
     Fused operands (pipelined kernel only; a launch that cannot take them raises):
     ``numer_slabs`` / ``numer_slab_stride``: ``numer`` is slab 0 of that many raw split-K
@@ -212,11 +211,14 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
                          col_mul=planes_colmul)
         return 1
     h = _hip
-    if solve_any_k(a, K):
+    nblocks = R if rep_index is None else int(rep_index.numel())
+    # (an empty launch returns below, once its operands are validated: planned as 1 x 1)
+    plan = solve_plan(a, K, max(n, 1), max(nblocks, 1), nsplit=nsplit, conv_mode=conv_mode,
+                      penalised=bool(l1_num or l1_den or l2), variant=variant, coop=coop,
+                      fused=fused, gram_of=gram is None and gram_of is not None,
+                      device=x.device)
+    if plan.kernel == "any":
         # ranks beyond the register-tiled kernels: library Gram-x GEMM + solve_any.hip
-        if fused or variant == "mfma":
-            raise ValueError(f"solve: K={K} runs the rank-general solve (solve_any.hip), "
-                             "which takes no fused operands / variant='mfma'")
         if gram is None:
             gram = _gram_op(gram_of, active=active)
         _solve_any(a, x, numer, gram, rep_index, max_iter, tol, l1_num, l1_den, l2, eps,
@@ -226,15 +228,8 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
                          col_mul=planes_colmul)
         return 1
     # a GPU operand the kernels do not cover is an error, never a silent eager fallback:
-    # fp32 only; K in 1..32 or a padded wide rank (the engine pads K <= 64 to a multiple
-    # of 8 and K <= 128 to a multiple of 16, models/nmf.py native_rank)
+    # fp32 only (every K without a tiled instantiation ran the rank-general solve above)
     _native_dtype_k("solve", x.dtype, K, h.solve_max_k())
-    if not h.solve_native_k(K):
-        raise ValueError(f"solve: K={K} has no kernel instantiation (pad it with zero "
-                         "components, see models.nmf.native_rank)")
-    if K > 64 and a != 0:
-        raise ValueError(f"solve: K={K} > 64 runs the matrix-core MU solve only "
-                         f"(algo={algo!r}); use algo='mu' or 'bpp'")
     _check_block_view("x", x, R, K, n)
     _check_block_view("numer", numer, R, K, n)
     if gram is not None:
@@ -251,10 +246,7 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
     if rep_index is not None:
         if rep_index.dtype != torch.int32 or rep_index.device != x.device:
             raise ValueError("rep_index must be int32 on the same device")
-        nblocks = int(rep_index.numel())
-        ri = rep_index.data_ptr()
-    else:
-        nblocks, ri = R, 0
+    ri = rep_index.data_ptr() if rep_index is not None else 0
     if nblocks == 0 or n == 0:
         return 0
     if nsplit > 1 and max_iter != 1:
@@ -270,50 +262,14 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
     f_args = _fused_solve_args(R, K, n, x, numer, numer_slabs, numer_slab_stride, numer_scale,
                                numer_base, numer_out, gram_parts, gram_parts_n, gram_out,
                                gram_parts_out) if fused else (1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
-    # matrix-core variant (csrc/kernels/solve_mfma.hip): MU with K <= 16 whenever every
-    # slice fits one 256-thread workgroup's register tiles; four of its workgroups are
-    # co-resident per CU, so its cooperative budget is 4x the 1024-thread one
-    S = None
-    rpl = 0
-    pipe_ok = (a == 0 and conv_mode == 1 and nsplit <= 1 and not (l1_num or l1_den or l2)
-               and _ENV["CNMF_SOLVE_PIPE"] != "0" and h.solve_pipe_k(K))
-    if variant in ("auto", "mfma") and a == 0 and h.solve_mfma_max_cols(K) > 0:
-        S = _mfma_split(n, nblocks, K, nsplit, coop, x.device)
-    if S is None and pipe_ok and variant in ("auto", "mfma"):
-        # the pipelined kernel alone (K > 16, or K <= 16 when every replicate's slices
-        # do not fit at once): co-resident rounds of `rpl` replicates
-        plan = _pipe_plan(n, nblocks, K, coop, x.device)
-        if plan is not None:
-            S, rpl = plan
-            if gram is None and gram_of is not None:
-                gram = _gram_op(gram_of, active=active)
-                gram_of = None
-    if fused and (S is None or not pipe_ok or gram_of is not None
-                  or h.solve_pipe_tiles(K, -(-n // S)) == 0):
-        raise ValueError("solve: fused operands need the pipelined MU kernel (K <= 64, "
-                         "l1 = l2 = 0, conv_mode 1, cooperative slices that fit)")
+    S = plan.slices if nsplit <= 1 else 1      # cooperative slices (nsplit's exchange nothing)
     if fused and gram_parts_out is not None and gram_parts_out.shape[1] < S:
         raise ValueError(f"gram_parts_out: {gram_parts_out.shape[1]} slots < {S} slices")
-    if S is not None:
-        vcode = 5 if _ENV["CNMF_SOLVE_PIPE"] == "0" else 3
-    elif gram is None:      # a VALU kernel: form the Gram first
-        gram = _gram_op(gram_of, active=active)
-    if S is not None:
-        pass
-    elif variant == "mfma":
-        raise ValueError(f"solve: variant 'mfma' does not cover algo={algo} K={K} n={n} "
-                         f"with {nblocks} replicates")
-    else:
-        vcode = {"auto": 0, "stream": 1, "reg": 2}[variant]
-        S = 1
-        if nsplit <= 1:
-            S = _coop_split(n, nblocks, x.device) if coop == "auto" else max(1, int(coop))
-        if S > 1 and nblocks * S > _coop_resident(x.device):
-            raise ValueError(f"coop={S} x {nblocks} blocks exceeds co-resident workgroups")
-    n_slice = (n + S - 1) // S
-    threads = min(h.solve_max_threads(K), max(64, ((min(n_slice, 4096 * 4) + 63) // 64) * 64))
-    ws_slots = ws_count = ws_flag = 0
-    epochs = 0
+    if gram is None and gram_of is not None and plan.kernel != "mfma":
+        # only solve_mfma.hip forms the Gram in its prologue
+        gram, gram_of = _gram_op(gram_of, active=active), None
+    ws_slots = ws_flag = epochs = gen = 0
+    gen_dev = (0, 0)
     if S > 1:
         epochs = (max_iter // max(1, check_every) + 3) if conv_mode == 1 else (max_iter + 2)
         ws = _coop_workspace(x.device, _stream_ptr(x), R, epochs, S)
@@ -327,12 +283,9 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
         else:
             ws["gen"] = ws["gen"] % 0x7FFFFFFE + 1   # tags this launch's arrivals (< 2^31)
             gen = ws["gen"]
-        ws_slots, ws_count, ws_flag = ws["slots"].data_ptr(), 0, ws["flag"].data_ptr()
+        ws_slots, ws_flag = ws["slots"].data_ptr(), ws["flag"].data_ptr()
         gen_dev = (ws["gen_dev"].data_ptr(), ws["arrive"].data_ptr()) if coop_device_gen \
             else (0, 0)
-    else:
-        gen = 0
-        gen_dev = (0, 0)
     pl_ptr = pl_rs = pl_ld = pl_plane = pl_cols = 0
     if planes is not None:
         if (planes.dtype != torch.int16 or planes.dim() != 3
@@ -358,12 +311,12 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
             lin_out.data_ptr() if lin_out is not None else 0,
             quad_out.data_ptr() if quad_out is not None else 0,
             iters_out.data_ptr() if iters_out is not None else 0, int(max(1, nsplit)),
-            int(conv_mode), int(check_every), int(threads), vcode,
-            active.data_ptr() if active is not None else 0, int(S), ws_slots, ws_count,
+            int(conv_mode), int(check_every), plan.threads, h.SOLVE_KERNEL_IDS[plan.kernel],
+            active.data_ptr() if active is not None else 0, int(S), ws_slots,
             int(gen), int(epochs), ws_flag, pl_ptr, int(pl_rs), int(pl_ld), int(pl_plane),
             planes_colmul.data_ptr() if (planes is not None and planes_colmul is not None) else 0,
             int(pl_cols), int(planes_n), gs_ptr, int(gs_rs), int(gs_ld), int(gs_cols),
-            *f_args, *gen_dev, int(rpl), _stamp_buffer(vcode, rpl, nblocks, S, K, x),
+            *f_args, *gen_dev, plan.reps_per_launch, _stamp_buffer(plan, nblocks, K, x),
             _stream_ptr(x))
     return int(S)
 
@@ -375,9 +328,10 @@ STAMP_LOG: list = []
 STAMPS_ON = False
 
 
-def _stamp_buffer(vcode, rpl, nblocks, S, K, x) -> int:
-    if not STAMPS_ON or vcode != 3 or torch.cuda.is_current_stream_capturing():
+def _stamp_buffer(plan, nblocks, K, x) -> int:
+    if not STAMPS_ON or plan.kernel != "pipe" or torch.cuda.is_current_stream_capturing():
         return 0
+    S, rpl = plan.slices, plan.reps_per_launch
     wgs = (rpl if rpl else nblocks) * max(1, int(S))
     buf = torch.zeros(wgs * 10, dtype=torch.int64, device=x.device)
     STAMP_LOG.append({"K": int(K), "S": int(S), "rounds": -(-nblocks // (rpl or nblocks)),
@@ -477,17 +431,18 @@ def _coop_resident(dev: torch.device) -> int:
     return max(1, _COOP_RESIDENT[key] // getattr(_TLS, "share", 1))
 
 
-def _coop_split(n: int, nblocks: int, dev: torch.device) -> int:
+def _coop_split(n: int, nblocks: int, dev, resident: int | None = None) -> int:
     if _ENV["CNMF_SOLVE_COOP"] == "0":
         return 1
+    resident = _coop_resident(dev) if resident is None else resident
     want = (n + COOP_COLS_PER_WG - 1) // COOP_COLS_PER_WG
-    return max(1, min(want, _coop_resident(dev) // max(1, nblocks), 16))
+    return max(1, min(want, resident // max(1, nblocks), 16))
 
 
 MFMA_WG_PER_CU = 4          # solve_mfma.hip: <= 128 VGPRs and <= 37 KB LDS per workgroup
 
 
-def _mfma_split(n: int, nblocks: int, K: int, nsplit: int, coop, dev: torch.device):
+def _mfma_split(n: int, nblocks: int, K: int, nsplit: int, coop, dev, resident=None):
     """Slices per replicate for the matrix-core solve, or None when it cannot run: with
     nsplit > 1 the caller's slices must each fit a workgroup; otherwise S cooperative
     slices (all co-resident) -- at least enough for the tiles, then more while the
@@ -496,15 +451,12 @@ def _mfma_split(n: int, nblocks: int, K: int, nsplit: int, coop, dev: torch.devi
     if nsplit > 1:   # fixed-step column split: no cooperative slices
         return 1 if -(-n // nsplit) <= cap else None
     s_min = -(-n // cap)
+    budget = MFMA_WG_PER_CU * (_coop_resident(dev) if resident is None else resident)
     if coop != "auto":
         S = max(1, int(coop))
-        return S if S >= s_min and (S == 1 or nblocks * S <= MFMA_WG_PER_CU *
-                                    _coop_resident(dev)) else None
-    if s_min > 1 and _ENV["CNMF_SOLVE_COOP"] == "0":
-        return None
-    if _ENV["CNMF_SOLVE_COOP"] == "0":
-        return 1            # s_min == 1 here: one workgroup per replicate, no exchange
-    budget = MFMA_WG_PER_CU * _coop_resident(dev)
+        return S if S >= s_min and (S == 1 or nblocks * S <= budget) else None
+    if _ENV["CNMF_SOLVE_COOP"] == "0":  # one workgroup per replicate, no exchange, or none
+        return 1 if s_min <= 1 else None
     if nblocks * s_min > budget and s_min > 1:
         return None
     S = max(s_min, min(budget // max(1, nblocks), -(-n // 256), 32))
@@ -513,17 +465,15 @@ def _mfma_split(n: int, nblocks: int, K: int, nsplit: int, coop, dev: torch.devi
 
 def pipe_slices(n: int, nblocks: int, K: int, dev: torch.device) -> int | None:
     """The slice count S an unregularised block-objective MU solve of ``nblocks``
-    replicates x ``n`` columns runs at under coop="auto" on the pipelined kernel (as
-    ops.solve picks it), or None when that kernel does not take it."""
-    if _hip is None or not _hip.solve_pipe_k(K) or _ENV["CNMF_SOLVE_PIPE"] == "0":
+    replicates x ``n`` columns runs at under coop="auto" on the pipelined kernel
+    (solve_plan), or None when that kernel does not take it."""
+    if _hip is None:
         return None
-    S = _mfma_split(n, nblocks, K, 1, "auto", dev) if _hip.solve_mfma_max_cols(K) > 0 else None
-    if S is None:
-        plan = _pipe_plan(n, nblocks, K, "auto", dev)
-        S = None if plan is None else plan[0]
-    if S is None or S > kCoopMaxSlices or _hip.solve_pipe_tiles(K, -(-n // S)) == 0:
+    try:
+        plan = solve_plan(ALGO_MU, K, n, nblocks, conv_mode=1, device=dev)
+    except ValueError:
         return None
-    return S
+    return plan.slices if plan.kernel == "pipe" else None
 
 
 def pipe_round_reps(n: int, K: int, dev: torch.device) -> int:
@@ -556,7 +506,7 @@ def _pipe_slice_cols(K: int) -> int:
     return 320 if 16 < K <= 32 else 640
 
 
-def _pipe_plan(n: int, nblocks: int, K: int, coop, dev: torch.device):
+def _pipe_plan(n: int, nblocks: int, K: int, coop, dev, resident=None):
     """(S, reps_per_launch) for the pipelined matrix-core solve (solve_pipe.h), or None.
     Every replicate's columns are split into S cooperative slices that each fit one
     workgroup's register tiles (S >= s_min); the launch runs the replicates in rounds of
@@ -568,7 +518,7 @@ def _pipe_plan(n: int, nblocks: int, K: int, coop, dev: torch.device):
     if cap <= 0 or nblocks <= 0:
         return None
     s_min = -(-n // cap)
-    budget = _hip.solve_pipe_wg_per_cu(K) * _coop_resident(dev)
+    budget = _hip.solve_pipe_wg_per_cu(K) * (_coop_resident(dev) if resident is None else resident)
     if s_min > kCoopMaxSlices or s_min > budget:
         return None
     if s_min > 1 and _ENV["CNMF_SOLVE_COOP"] == "0":
@@ -587,6 +537,81 @@ def _pipe_plan(n: int, nblocks: int, K: int, coop, dev: torch.device):
     if S == 1:              # no cooperative exchange: residency does not matter
         return 1, 0
     return S, (rpl if rpl < nblocks else 0)
+
+
+class SolvePlan(NamedTuple):
+    """What one fused inner solve launches (:func:`solve_plan`)."""
+    kernel: str             # "any" (solve_any.hip) or a key of _hip.SOLVE_KERNEL_IDS
+    slices: int             # S: column slices per replicate (cooperative, or nsplit's)
+    reps_per_launch: int    # pipelined kernel's launch rounds, 0 = one round
+    threads: int            # workgroup size of the VALU kernels, else 0
+
+
+def solve_plan(algo, K: int, n: int, nblocks: int, *, nsplit: int = 1, conv_mode: int = 0,
+               penalised: bool = False, variant: str = "auto", coop: int | str = "auto",
+               fused: bool = False, gram_of: bool = False, device=None,
+               resident: int | None = None) -> SolvePlan:
+    """The one place that picks the kernel and slicing of :func:`solve` for ``nblocks``
+    replicates x ``n`` columns: ops.solve launches what this returns and cnmf_solve
+    (csrc/kernels/solve.hip) obeys.  The rules: docs/ARCHITECTURE.md, "Solve dispatch".
+    ``penalised``: l1_num, l1_den or l2 != 0; ``fused``: fused operands; ``gram_of``: the
+    system matrix comes as a factor; ``resident``: the co-residency budget (default: the
+    device's).  ValueError for a combination no kernel takes."""
+    h = _require_native()
+    a = ALGOS.get(algo, algo)
+    if variant not in ("auto", "stream", "reg", "mfma"):
+        raise ValueError(f"solve: unknown variant {variant!r}")
+    if solve_any_k(a, K):
+        if fused or variant == "mfma":
+            raise ValueError(f"solve: K={K} runs the rank-general solve (solve_any.hip), "
+                             "which takes no fused operands / variant='mfma'")
+        return SolvePlan("any", 1, 0, 0)
+    if resident is None:
+        resident = _coop_resident(device if device is not None else torch.device("cuda"))
+    # matrix-core kernels, MU only: solve_mfma.hip (K <= 16) whenever every slice fits one
+    # 256-thread workgroup's register tiles, or in its place the pipelined kernel where that
+    # covers the solve; past solve_mfma's reach (K > 16, or the slices not all resident at
+    # once) the pipelined kernel alone, in co-resident rounds of `rpl` replicates
+    kernel, rpl = None, 0
+    if a == ALGO_MU and variant in ("auto", "mfma"):
+        pipe_ok = (conv_mode == 1 and nsplit <= 1 and not penalised
+                   and _ENV["CNMF_SOLVE_PIPE"] != "0" and h.solve_pipe_k(K))
+        S = _mfma_split(n, nblocks, K, nsplit, coop, device, resident) \
+            if h.solve_mfma_max_cols(K) > 0 else None
+        if S is not None:
+            kernel = "pipe" if (pipe_ok and not gram_of
+                                and h.solve_pipe_tiles(K, -(-n // S)) > 0) else "mfma"
+        elif pipe_ok:
+            rounds = _pipe_plan(n, nblocks, K, coop, device, resident)
+            if rounds is not None:
+                kernel, (S, rpl) = "pipe", rounds
+    if fused and kernel != "pipe":
+        raise ValueError("solve: fused operands need the pipelined MU kernel (K <= 64, "
+                         "l1 = l2 = 0, conv_mode 1, cooperative slices that fit)")
+    threads = 0
+    if kernel is None:
+        if variant == "mfma":
+            raise ValueError(f"solve: variant 'mfma' does not cover algo={algo} K={K} n={n} "
+                             f"with {nblocks} replicates")
+        S = 1 if nsplit > 1 else _coop_split(n, nblocks, device, resident) if coop == "auto" \
+            else max(1, int(coop))
+        if S > 1 and nblocks * S > resident:
+            raise ValueError(f"coop={S} x {nblocks} blocks exceeds co-resident workgroups")
+        if K > 64:
+            kernel = "wmfma_bf16" if variant != "stream" and K % 32 == 0 else "wmfma_f32"
+        elif K > 32:
+            kernel = "wide"
+        elif variant == "reg" or (variant == "auto" and
+                                  -(-n // max(S, nsplit)) <= h.solve_reg_max_cols(K)):
+            kernel = "resident"     # "reg" forces it: the launcher rejects a slice too wide
+        else:
+            kernel = "stream"
+        if K <= 64:
+            threads = min(h.solve_max_threads(K),
+                          max(64, ((min(-(-n // S), 4096 * 4) + 63) // 64) * 64))
+    if S > kCoopMaxSlices:
+        raise ValueError(f"solve: {S} cooperative slices exceed the kernels' {kCoopMaxSlices}")
+    return SolvePlan(kernel, max(S, nsplit), rpl, threads)
 
 
 def _coop_workspace(dev: torch.device, stream: int, R: int, epochs: int, S: int) -> dict:

@@ -85,14 +85,18 @@ PYBIND11_MODULE(_hip, m) {
   m.def("solve_pipe_max_cols", [](int K) { return cnmf_solve_pipe_max_cols(K); });
   m.def("solve_pipe_wg_per_cu", [](int K) { return cnmf_solve_pipe_wg_per_cu(K); });
 
+  py::dict ids;   // kernel name -> the id cnmf_solve takes (launchers.h)
+#define CNMF_SOLVE_KERNEL_ID(name) ids[#name] = (int)CNMF_SOLVE_##name;
+  CNMF_SOLVE_KERNELS(CNMF_SOLVE_KERNEL_ID)
+#undef CNMF_SOLVE_KERNEL_ID
+  m.attr("SOLVE_KERNEL_IDS") = ids;
   m.def("solve",
         [](int algo, int K, uintptr_t x, long long x_rs, long long ldx, uintptr_t numer,
            long long n_rs, long long ldn, uintptr_t gram, long long g_rs, uintptr_t rep_index,
            int nblocks, int ncols, int max_iter, float tol, float l1_num, float l1_den, float l2,
            float eps, uintptr_t lin_out, uintptr_t quad_out, uintptr_t iters_out, int nsplit,
-           int conv_mode, int check_every, int threads, int variant, uintptr_t active,
-           int coop_split, uintptr_t coop_slots, uintptr_t coop_count, unsigned coop_gen,
-           int coop_epochs,
+           int conv_mode, int check_every, int threads, int kernel, uintptr_t active,
+           int coop_split, uintptr_t coop_slots, unsigned coop_gen, int coop_epochs,
            uintptr_t coop_timeout, uintptr_t planes, long long pl_rs, long long pl_ld,
            long long pl_plane, uintptr_t pl_colmul, int pl_cols, int pl_n, uintptr_t gsrc,
            long long gs_rs, long long gs_ld, int gs_cols, int nslab_n, long long nslab_stride,
@@ -104,9 +108,8 @@ PYBIND11_MODULE(_hip, m) {
                            P<const float>(gram), g_rs, P<const int>(rep_index), nblocks, ncols,
                            max_iter, tol, l1_num, l1_den, l2, eps, P<float>(lin_out),
                            P<float>(quad_out), P<int>(iters_out), nsplit, conv_mode,
-                           check_every, threads, variant, P<const int>(active), coop_split,
-                           P<float>(coop_slots), P<unsigned long long>(coop_count), coop_gen,
-                           coop_epochs,
+                           check_every, threads, kernel, P<const int>(active), coop_split,
+                           P<float>(coop_slots), coop_gen, coop_epochs,
                            P<int>(coop_timeout), P<unsigned short>(planes), pl_rs, pl_ld,
                            pl_plane, P<const float>(pl_colmul), pl_cols, pl_n,
                            P<const float>(gsrc), gs_rs, gs_ld, gs_cols, nslab_n, nslab_stride,

@@ -9,14 +9,22 @@ extern "C" {
 int cnmf_solve_max_k();
 int cnmf_solve_max_threads(int K);
 int cnmf_solve_native_k(int K);
+// The solve kernels cnmf_solve launches, named once: the enum below, the binding's
+// SOLVE_KERNEL_IDS (name -> id) and through it ops.SolvePlan.kernel all come from this list
+#define CNMF_SOLVE_KERNELS(X) \
+  X(pipe) X(mfma) X(wmfma_bf16) X(wmfma_f32) X(wide) X(resident) X(stream)
+enum cnmf_solve_kernel {
+#define CNMF_SOLVE_KERNEL_ID(name) CNMF_SOLVE_##name,
+  CNMF_SOLVE_KERNELS(CNMF_SOLVE_KERNEL_ID)
+#undef CNMF_SOLVE_KERNEL_ID
+};
 hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long long ldx, const float* numer,
                       long long n_rs, long long ldn, const float* gram, long long g_rs,
                       const int* rep_index, int nblocks, int ncols, int max_iter, float tol,
                       float l1_num, float l1_den, float l2, float eps, float* lin_out,
                       float* quad_out, int* iters_out, int nsplit, int conv_mode,
-                      int check_every, int threads, int variant, const int* active,
-                      int coop_split, float* coop_slots, unsigned long long* coop_count,
-                      unsigned coop_gen, int coop_epochs,
+                      int check_every, int threads, int kernel, const int* active,
+                      int coop_split, float* coop_slots, unsigned coop_gen, int coop_epochs,
                       int* coop_timeout, unsigned short* planes, long long pl_rs,
                       long long pl_ld, long long pl_plane, const float* pl_colmul,
                       int pl_cols, int pl_n, const float* gsrc, long long gs_rs,

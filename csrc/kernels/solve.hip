@@ -1,5 +1,6 @@
 // Launcher + C ABI of the fused inner solve (kernels in solve_core.h).  This unit
 // instantiates the streaming variant; solve_res.hip the register-resident one.
+#include "launchers.h"
 #include "solve_core.h"
 
 namespace cnmf {
@@ -10,10 +11,6 @@ hipError_t launch_solve_stream(int K, int algo, const SolveParams& p, int nblock
 }  // namespace cnmf
 
 extern "C" int cnmf_solve_max_k() { return 128; }
-extern "C" int cnmf_solve_mfma_max_cols(int K);
-extern "C" int cnmf_solve_pipe_tiles(int K, int per);
-extern "C" int cnmf_solve_pipe_k(int K);
-extern "C" int cnmf_solve_pipe_wg_per_cu(int K);
 
 // ranks the kernels are instantiated for: 1..32, the padded wide ranks 40..64 (multiples
 // of 8) and 80..128 (multiples of 16, MU only: solve_wmfma.hip)
@@ -34,10 +31,9 @@ extern "C" hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long
                                  int nblocks, int ncols, int max_iter, float tol, float l1_num,
                                  float l1_den, float l2, float eps, float* lin_out,
                                  float* quad_out, int* iters_out, int nsplit, int conv_mode,
-                                 int check_every, int threads, int variant,
+                                 int check_every, int threads, int kernel,
                                  const int* active, int coop_split, float* coop_slots,
-                                 unsigned long long* coop_count, unsigned coop_gen,
-                                 int coop_epochs, int* coop_timeout,
+                                 unsigned coop_gen, int coop_epochs, int* coop_timeout,
                                  unsigned short* planes, long long pl_rs, long long pl_ld,
                                  long long pl_plane, const float* pl_colmul, int pl_cols,
                                  int pl_n, const float* gsrc, long long gs_rs, long long gs_ld,
@@ -64,7 +60,6 @@ extern "C" hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long
   p.check_every = check_every;
   p.active = active;
   p.coop_slots = coop_split > 1 ? (unsigned long long*)coop_slots : nullptr;
-  (void)coop_count;   // unused since the granule exchange (kept in the C ABI)
   p.coop_gen = coop_gen;
   p.coop_epochs = coop_epochs;
   p.coop_timeout = coop_timeout;
@@ -80,44 +75,41 @@ extern "C" hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long
   p.coop_gen_dev = coop_split > 1 ? coop_gen_dev : nullptr;
   p.coop_arrive = coop_arrive;
   p.stamps = stamps;
-  {
-    // workgroup order of the pipelined kernel (SolveParams.pipe_map); CNMF_PIPE_MAP
-    // overrides the default for A/B runs
-    static const int map_env = [] {
-      const char* e = getenv("CNMF_PIPE_MAP");
-      return (e && *e) ? atoi(e) : -1;
-    }();
-    p.pipe_map = map_env >= 0 ? map_env : -1;     // -1: chosen per launch below
-    p.pipe_nblocks = nblocks;
-  }
+  // workgroup order of the pipelined kernel (SolveParams.pipe_map); CNMF_PIPE_MAP
+  // overrides the default for A/B runs
+  static const int map_env = [] {
+    const char* e = getenv("CNMF_PIPE_MAP");
+    return (e && *e) ? atoi(e) : -1;
+  }();
+  p.pipe_map = map_env;     // < 0: chosen per launch below
+  p.pipe_nblocks = nblocks;
   if (p.coop_gen_dev && !coop_arrive) return hipErrorInvalidValue;
   const bool fused = p.nslab_n > 1 || n_scale || nbase || nout || gpart || gout || gp_out ||
                      (coop_split > 1 && coop_gen_dev);
   if (fused && (p.nslab_n > 1 && p.nslab_stride * 4 * (long long)p.nslab_n >= 0x7fffffffLL))
     return hipErrorInvalidValue;
-  if (!gram && !gpart && !gsrc) return hipErrorInvalidValue;
-  // the in-prologue Gram is a matrix-core kernel feature (K <= 16)
-  if (gsrc && (variant != 3 || K > 16 || gs_cols < 1)) return hipErrorInvalidValue;
   if (planes && pl_cols < ncols) return hipErrorInvalidValue;
   if (coop_split > 1 && nsplit > 1) return hipErrorInvalidValue;
   if (coop_split > cnmf::kCoopMaxSlices) return hipErrorInvalidValue;
   if (!cnmf_solve_native_k(K)) return hipErrorInvalidValue;
-  if (variant == 3 || variant == 5) {
-    // matrix-core variants, MU, every slice within one workgroup's tiles; the host picks
-    // the slicing (ops.solve / _mfma_split / _pipe_plan).  The software-pipelined kernel
-    // (solve_pipe.h, K <= 64) takes the unregularised block-objective solves;
-    // solve_mfma.hip (K <= 16) the rest (and everything under variant 5 =
-    // CNMF_SOLVE_PIPE=0).  reps_per_launch > 0: the pipelined kernel runs the replicates
-    // in rounds of that many, each round's S * reps workgroups co-resident (the host's
-    // budget) -- the wide ranks' register tiles do not hold every replicate at once
-    const int parts = nsplit > 1 ? nsplit : (coop_split > 1 ? coop_split : 1);
-    const int per = (ncols + parts - 1) / parts;
-    const int T = ((per + 15) / 16 + 3) / 4;
-    if (algo != 0) return hipErrorInvalidValue;
-    const int Tp = cnmf_solve_pipe_tiles(K, per);
-    const bool pipe = variant == 3 && Tp > 0 && conv_mode == 1 && nsplit <= 1 && !gsrc &&
-                      l1_num == 0.f && l1_den == 0.f && l2 == 0.f;
-    if (pipe) {
+  // `kernel` is the host planner's choice (ops.solve_plan; the rules are the table "Solve
+  // dispatch" in docs/ARCHITECTURE.md).  Each case checks that kernel's own preconditions
+  // -- a failed one is an error, never another kernel -- and derives only what follows from
+  // its geometry (tiles, columns per thread, workgroup order).
+  const int parts = nsplit > 1 ? nsplit : (coop_split > 1 ? coop_split : 1);
+  const int per = (ncols + parts - 1) / parts;
+  // the in-prologue Gram is solve_mfma's; fused operands and launch rounds (reps_per_launch
+  // replicates at a time, each round co-resident) the pipelined kernel's: never dropped
+  if (gsrc && (kernel != CNMF_SOLVE_mfma || gs_cols < 1)) return hipErrorInvalidValue;
+  if (kernel != CNMF_SOLVE_pipe &&
+      (fused || (!gram && !gsrc) || (reps_per_launch > 0 && reps_per_launch < nblocks)))
+    return hipErrorInvalidValue;
+  switch (kernel) {
+    case CNMF_SOLVE_pipe: {   // solve_pipe.h: unregularised block-objective MU, K <= 64
+      const int Tp = cnmf_solve_pipe_tiles(K, per);
+      if (algo != 0 || Tp == 0 || conv_mode != 1 || nsplit > 1 || l1_num != 0.f ||
+          l1_den != 0.f || l2 != 0.f || (!gram && !gpart))
+        return hipErrorInvalidValue;
       const int rpl = reps_per_launch > 0 ? reps_per_launch : nblocks;
       if (p.pipe_map < 0) {
         // XCD-grouped slices (one L2 for a replicate's exchanges: the objective checks
@@ -126,16 +118,12 @@ extern "C" hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long
         // 13,482-13,535 rep/s, K=5..13 grid 18,972 -> 19,677; launches in several rounds
         // (K = 20 / 30 usage side) lost with it (r4g, r4z), so they keep the plain order
         static int n_cu[16] = {0};
-        int dev = 0;
+        int dev = 0, v = 0;
         (void)hipGetDevice(&dev);
         if (dev < 0 || dev >= 16) dev = 0;
-        if (n_cu[dev] == 0) {
-          int v = 0;
-          if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-              v <= 0)
-            v = 256;
-          n_cu[dev] = v;
-        }
+        if (n_cu[dev] == 0)
+          n_cu[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) ==
+                              hipSuccess && v > 0 ? v : 256;
         const int S = coop_split > 1 ? coop_split : 1;
         const long long per_xcd = (long long)cnmf_solve_pipe_wg_per_cu(K) * n_cu[dev] / 8;
         p.pipe_map = (S > 1 && rpl >= nblocks && (long long)((rpl + 7) / 8) * S <= per_xcd) ? 1 : 0;
@@ -148,33 +136,35 @@ extern "C" hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long
       }
       return hipSuccess;
     }
-    if (reps_per_launch > 0 && reps_per_launch < nblocks) return hipErrorInvalidValue;
-    if (per > cnmf_solve_mfma_max_cols(K)) return hipErrorInvalidValue;
-    // the fused operands exist only in the pipelined kernel: never drop them silently
-    if (fused || (!gram && !gsrc)) return hipErrorInvalidValue;
-    return cnmf::launch_solve_mfma(K, p, nblocks, T < 1 ? 1 : T, stream);
+    case CNMF_SOLVE_mfma: {   // solve_mfma.hip: MU, K <= 16, penalties, nsplit, in-prologue Gram
+      if (algo != 0 || per > cnmf_solve_mfma_max_cols(K)) return hipErrorInvalidValue;
+      const int T = ((per + 15) / 16 + 3) / 4;
+      return cnmf::launch_solve_mfma(K, p, nblocks, T < 1 ? 1 : T, stream);
+    }
+    // K > 64: the matrix-core wide solve, MU only (HALS is Gauss-Seidel over components).
+    // Split-bf16 Gram apply at K = 96 / 128 (whole 32-deep k-blocks); fp32 MFMA at 80 / 112:
+    // padding those to 96 / 128 inside the kernel cost occupancy and measured slower
+    // (profiles/r3af_*)
+    case CNMF_SOLVE_wmfma_bf16:
+    case CNMF_SOLVE_wmfma_f32: {
+      const bool bf16 = kernel == CNMF_SOLVE_wmfma_bf16;
+      if (algo != 0 || (bf16 && K % 32 != 0)) return hipErrorInvalidValue;
+      return cnmf::launch_solve_wmfma(K, p, nblocks, bf16, stream);
+    }
+    case CNMF_SOLVE_wide:
+      return cnmf::launch_solve_wide(K, algo, p, nblocks, threads, stream);
+    case CNMF_SOLVE_resident: {
+      // every slice must fit U <= res_max_cols(K) columns per thread of a <= 1024-thread
+      // workgroup; it runs with the smallest such U and just enough threads for the slice
+      const int U = per <= 1024 ? 1 : (per + 1023) / 1024;
+      if (K > cnmf::kResidentMaxK || U > cnmf::res_max_cols(K)) return hipErrorInvalidValue;
+      int t_res = (((per + U - 1) / U + 63) / 64) * 64;
+      if (t_res < 64) t_res = 64;
+      return cnmf::launch_solve_resident(K, U, algo, p, nblocks, t_res, stream);
+    }
+    case CNMF_SOLVE_stream:
+      return cnmf::launch_solve_stream(K, algo, p, nblocks, threads, stream);
+    default:
+      return hipErrorInvalidValue;
   }
-  if (fused || !gram) return hipErrorInvalidValue;
-  // K > 64: the matrix-core wide solve, MU only (HALS is Gauss-Seidel over components).
-  // Split-bf16 Gram apply at K = 96 / 128 (whole 32-deep k-blocks); fp32 MFMA at 80 / 112
-  // and under variant 1 (streaming): padding those to 96 / 128 inside the kernel cost
-  // occupancy and measured slower (profiles/r3af_*)
-  if (K > 64)
-    return algo == 0 ? cnmf::launch_solve_wmfma(K, p, nblocks, variant != 1 && K % 32 == 0, stream)
-                     : hipErrorInvalidValue;
-  if (K > 32) return cnmf::launch_solve_wide(K, algo, p, nblocks, threads, stream);
-  // variant: 0 auto, 1 streaming, 2 register-resident (3 = mfma above).  Resident needs every slice to
-  // fit U <= res_max_cols(K) columns per thread of a <= 1024-thread workgroup; it runs
-  // with the smallest such U and just enough threads for the slice.
-  const int parts = nsplit > 1 ? nsplit : (coop_split > 1 ? coop_split : 1);
-  const int per = (ncols + parts - 1) / parts;
-  const int U = per <= 1024 ? 1 : (per + 1023) / 1024;
-  const bool fits = K <= cnmf::kResidentMaxK && U <= cnmf::res_max_cols(K);
-  if (variant == 2 && !fits) return hipErrorInvalidValue;
-  if ((variant == 0 && fits) || variant == 2) {
-    int t_res = (((per + U - 1) / U + 63) / 64) * 64;
-    if (t_res < 64) t_res = 64;
-    return cnmf::launch_solve_resident(K, U, algo, p, nblocks, t_res, stream);
-  }
-  return cnmf::launch_solve_stream(K, algo, p, nblocks, threads, stream);
 }

@@ -30,16 +30,24 @@ def _fixed(algo, K, n, pens, **kw):
     return DevSolve(DEV, algo, *solve_problem(R, K, n, seed=K), **kw)(pens, 6)[0]
 
 
+def _plan(algo, K, n, **kw):
+    """What ops.solve launches for the penalised solves of one case (``kw`` as passed to
+    check_solve_case / _fixed): the same under both stop rules."""
+    plans = {ops.solve_plan(algo, K, n, R, penalised=True, conv_mode=c, **kw) for c in (0, 1)}
+    assert len(plans) == 1, plans
+    return plans.pop()
+
+
 # ------------------------------------------------------------------------- A. ops.solve
 @pytest.mark.parametrize("K", [3, 10, 16])
 def test_solve_mfma_penalised(K):
     """solve_mfma.hip (MU, K <= 16, variant 'auto').  A penalised MU solve never takes the
-    pipelined kernel, which has no penalty terms: cnmf_solve sends l1 / l2 != 0 to
-    solve_mfma.hip, and a launch that ignored them would miss the reference by >= 20x the
-    tolerance (the guard)."""
+    pipelined kernel, which has no penalty terms, and a launch that ignored them would miss
+    the reference by >= 20x the tolerance (the guard)."""
     dev = torch.device(DEV)
-    S = ops._mfma_split(777, R, K, 1, "auto", dev)       # cooperative slices of <= 768 columns
-    assert S is not None and 0 < -(-777 // S) <= ops._hip.solve_mfma_max_cols(K)
+    plan = _plan("mu", K, 777)                          # cooperative slices of <= 768 columns
+    assert plan.kernel == "mfma"
+    assert 0 < -(-777 // plan.slices) <= ops._hip.solve_mfma_max_cols(K)
     check_solve_case(DEV, "mu", K, 777)
     ops.coop_check(dev)
 
@@ -48,7 +56,7 @@ def test_solve_mfma_penalised(K):
 @pytest.mark.parametrize("K", [3, 10, 17, 32])
 def test_solve_streaming_penalised(algo, K):
     """solve.hip, the streaming VALU kernel (variant 'stream', K <= 32)."""
-    assert K <= 32 and not ops.solve_any_k(ops.ALGOS[algo], K)
+    assert _plan(algo, K, 777, variant="stream").kernel == "stream"
     check_solve_case(DEV, algo, K, 777, variant="stream")
 
 
@@ -58,6 +66,8 @@ def test_solve_resident_penalised(algo, K):
     """solve_res*.hip with one column per thread (variant 'reg' raises when the slice does
     not fit the resident kernel)."""
     assert ops._hip.solve_reg_max_cols(K) >= 777
+    plan = _plan(algo, K, 777, variant="reg", coop=1)
+    assert (plan.kernel, plan.slices) == ("resident", 1)
     check_solve_case(DEV, algo, K, 777, variant="reg", coop=1)
 
 
@@ -68,6 +78,8 @@ def test_solve_resident_lds_numerator_penalised(algo):
     streaming kernel on the fixed steps, as the unpenalised test asserts."""
     K, n = 10, 2600
     assert 2048 < n <= ops._hip.solve_reg_max_cols(K) == 3072
+    assert _plan(algo, K, n, variant="reg", coop=1).kernel == "resident"
+    assert _plan(algo, K, n, variant="stream", coop=1).kernel == "stream"
     out = check_solve_case(DEV, algo, K, n, variant="reg", coop=1)
     for pens, x in out.items():
         assert torch.equal(x, _fixed(algo, K, n, pens, variant="stream", coop=1)), pens
@@ -77,7 +89,7 @@ def test_solve_resident_lds_numerator_penalised(algo):
 @pytest.mark.parametrize("K", [40, 48, 64])
 def test_solve_wide_penalised(algo, K):
     """solve_wide.hip (32 < K <= 64; a penalised MU solve has no matrix-core route there)."""
-    assert ops._hip.solve_mfma_max_cols(K) == 0 and ops._hip.solve_native_k(K)
+    assert _plan(algo, K, 777).kernel == "wide"
     check_solve_case(DEV, algo, K, 777)
 
 
@@ -89,7 +101,8 @@ def test_solve_wmfma_penalised(K, variant):
     float64 reference by only 18 / 9 / 25 x that tolerance at K = 80 and 14 / 6.5 / 21 x at
     K = 96 (l1_num / l1_den / l2), so these cases run 4 P = (40, 20, 40): 78 / 35 / 89 x and
     59 / 27 / 77 x."""
-    assert K > 64 and not ops.solve_any_k(ops.ALGOS["mu"], K)
+    bf16 = variant == "auto" and K == 96
+    assert _plan("mu", K, 777, variant=variant).kernel == ("wmfma_bf16" if bf16 else "wmfma_f32")
     check_solve_case(DEV, "mu", K, 777, scale=4.0, t=TOL_WMFMA, variant=variant)
 
 
@@ -99,7 +112,7 @@ def test_solve_any_rank_penalised(algo, K):
     tolerances of test_solve_any_rank_matches_float64_reference.  P = (10, 5, 10) moves
     the float64 reference by 50 / 23 / 64 x that tolerance at MU K = 37 and by > 2000 x at
     HALS K = 80."""
-    assert ops.solve_any_k(ops.ALGOS[algo], K)
+    assert _plan(algo, K, 777).kernel == "any"
     check_solve_case(DEV, algo, K, 777, t=TOL_ANY)
 
 
@@ -112,9 +125,13 @@ def test_solve_cooperative_slices_penalised(algo, K, variants):
     the matrix-core kernel's 768), solve_wide at K = 40 -- and per VALU kernel the fixed
     steps bitwise equal to one workgroup per replicate."""
     n, dev = 2600, torch.device(DEV)
-    assert ops._hip.solve_mfma_max_cols(K) == 0 or ops._mfma_split(n, R, K, 1, 3, dev) is None
+    plan = _plan(algo, K, n, coop=3)
+    assert (plan.kernel, plan.slices) == ("resident" if K == 10 else "wide", 3)
     check_solve_case(DEV, algo, K, n, coop=3)
     for variant in variants:
+        plan = _plan(algo, K, n, variant=variant, coop=3)
+        assert (plan.kernel, plan.slices) == (
+            {"stream": "stream", "reg": "resident", "auto": "wide"}[variant], 3)
         for pens in SOLVE_SETS:
             a = _fixed(algo, K, n, pens, variant=variant, coop=3)
             assert torch.equal(a, _fixed(algo, K, n, pens, variant=variant, coop=1)), pens
@@ -125,7 +142,8 @@ def test_solve_mfma_cooperative_slices_penalised():
     """MU K = 10, n = 2600 with four cooperating workgroups: slices of 650 columns, the
     matrix-core kernel's cooperative path under penalties (parts 1-3)."""
     dev = torch.device(DEV)
-    assert ops._mfma_split(2600, R, 10, 1, 4, dev) == 4
+    plan = _plan("mu", 10, 2600, coop=4)
+    assert (plan.kernel, plan.slices) == ("mfma", 4)
     check_solve_case(DEV, "mu", 10, 2600, coop=4)
     ops.coop_check(dev)
 
@@ -136,9 +154,9 @@ def test_solve_column_split_penalised(K, n):
     lin / quad summed by atomics.  At n = 2600 a slice (867 columns) exceeds the
     matrix-core kernel's 768, so K = 10 runs the VALU split and K = 40 solve_wide's; at
     n = 2100 (700 columns) K = 10 runs solve_mfma's split."""
-    split = ops._mfma_split(n, R, K, 3, "auto", torch.device(DEV)) \
-        if ops._hip.solve_mfma_max_cols(K) > 0 else None
-    assert (split is not None) == (n == 2100)
+    plan = _plan("mu", K, n, nsplit=3)
+    assert (plan.kernel, plan.slices) == (
+        {(10, 2600): "resident", (40, 2600): "wide", (10, 2100): "mfma"}[K, n], 3)
     check_solve_nsplit(DEV, K, n)
 
 

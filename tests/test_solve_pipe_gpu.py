@@ -35,7 +35,10 @@ def test_solve_pipe_wide_k_matches_reference(K):
     x0, numer, gram = _problem(R, K, n, seed=300 + K)
     dev = torch.device("cuda")
     numer_d, gram_d = numer.to(dev), gram.to(dev)
-    assert ops.pipe_slices(n, R, K, dev) is not None
+    plan = ops.solve_plan("mu", K, n, R, conv_mode=1)
+    assert plan.kernel == "pipe" and ops.pipe_slices(n, R, K, dev) == plan.slices
+    assert ops.solve_plan("mu", K, n, R, conv_mode=1, variant="stream").kernel == (
+        "stream" if K <= 32 else "wide")
     outs = {}
     for variant in ("auto", "stream"):
         xg = x0.clone().to(dev)
@@ -92,6 +95,7 @@ def test_solve_pipe_launch_rounds_bitwise_one_launch(monkeypatch, K):
         assert plan is not None and plan[0] == S
         if resident != full:
             assert 0 < plan[1] < ri.numel()      # several rounds
+        assert ops.solve_plan("mu", K, n, ri.numel(), conv_mode=1, coop=S) == ("pipe", *plan, 0)
         xg = x0.clone().to(dev)
         lin = torch.zeros(R, device=dev)
         quad = torch.zeros(R, device=dev)
