@@ -76,6 +76,14 @@ class NMFOptions:
     # replicate is linear in the density on the CSR side and flat on the dense one, equal
     # near 14 % (K = 48) and 10.7 % (K = 64); one threshold below both
     kl_sparse_density_wide: float = 0.10
+    # the same threshold for 64 < K <= 128 (sparse_kl_xwide.hip); above K = 64 the dense
+    # route is the rank-general one (beta_any.hip).  Measured (profiles/p3_kl_xwide_ab.txt;
+    # CSR vs dense rep/s): K = 80: 8 % 52.6 / 12.2, 15 % 33.9 / 11.9, 25 % 22.7 / 11.9,
+    # 35 % 17.4 / 11.8; K = 128: 8 % 34.3 / 9.8, 15 % 21.4 / 9.6, 25 % 13.9 / 9.5,
+    # 35 % 10.4 / 9.4 -- the CSR route wins at every measured density (the linear fits
+    # would meet near 54 % and 39 %, beyond the measurements), so the threshold is the
+    # highest density measured
+    kl_sparse_density_xwide: float = 0.35
 
     @classmethod
     def from_kwargs(cls, n_components: int, **kw) -> "NMFOptions":

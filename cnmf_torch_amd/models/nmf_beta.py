@@ -61,13 +61,14 @@ class _BetaMixin:
 
     def _kl_sparse(self):
         """CSR of X (ops.KLCSR) when the KL MU statistics run on the sparse kernels
-        (sparse_kl.hip, sparse_kl_wide.hip above K = 32): KL on the native GPU path at
-        K <= 64 with X at most ``kl_sparse_density`` non-zero (``kl_sparse_density_wide``
-        for 32 < K <= 64; ``CNMF_KL_SPARSE=1`` forces it, ``=0`` disables it); else None
-        (dense split-precision kernels).  The density is read once per solver (one host
-        sync), the route decided once per rank."""
+        (sparse_kl.hip, sparse_kl_wide.hip above K = 32, sparse_kl_xwide.hip above K = 64):
+        KL on the native GPU path at K <= 128 with X at most ``kl_sparse_density`` non-zero
+        (``kl_sparse_density_wide`` for 32 < K <= 64, ``kl_sparse_density_xwide`` for
+        64 < K <= 128; ``CNMF_KL_SPARSE=1`` forces it, ``=0`` disables it); else None
+        (dense split-precision kernels, beta_any.hip above K = 64).  The density is read once
+        per solver (one host sync), the route decided once per rank tier."""
         K = max(getattr(self, "_beta_K", 0), self.opts.n_components)
-        if K > 64:                               # the CSR kernels stop at K = 64
+        if K > 128:                              # the CSR kernels stop at K = 128
             return None
         if "_kl_route" not in self.__dict__:
             X = self.X
@@ -78,13 +79,14 @@ class _BetaMixin:
             if (self.beta == 1.0 and isinstance(X, torch.Tensor) and X.device.type == "cuda"
                     and X.dtype == torch.float32 and ops.use_native(X)):
                 self._kl_dens = float((X != 0).sum()) / max(X.numel(), 1)
-        wide = K > 32
-        if wide not in self._kl_route:
+        tier = 0 if K <= 32 else 1 if K <= 64 else 2
+        if tier not in self._kl_route:
             env = os.environ.get("CNMF_KL_SPARSE", "")
-            cap = self.opts.kl_sparse_density_wide if wide else self.opts.kl_sparse_density
-            self._kl_route[wide] = (self._kl_dens is not None and env != "0"
+            cap = (self.opts.kl_sparse_density, self.opts.kl_sparse_density_wide,
+                   self.opts.kl_sparse_density_xwide)[tier]
+            self._kl_route[tier] = (self._kl_dens is not None and env != "0"
                                     and (env == "1" or self._kl_dens <= float(cap)))
-        if not self._kl_route[wide]:
+        if not self._kl_route[tier]:
             return None
         if self._kl_csr is None:
             self._kl_csr = ops.kl_csr(self.X)

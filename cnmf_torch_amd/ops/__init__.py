@@ -1355,7 +1355,7 @@ def beta_w_partials(X: torch.Tensor, XT: torch.Tensor | None, HT3: torch.Tensor,
 # ------------------------------------------------------------- sparse KL (CSR X)
 class KLCSR(NamedTuple):
     """CSR of a non-negative matrix for the sparse KL kernels (sparse_kl.hip, K <= 32;
-    sparse_kl_wide.hip, 33 <= K <= 64): row i owns
+    sparse_kl_wide.hip, 33 <= K <= 64; sparse_kl_xwide.hip, 65 <= K <= 128): row i owns
     entries [rowptr[i], rowptr[i+1]) of col / val; a row range is a rowptr slice over the
     same col / val (:func:`kl_csr_rows`)."""
     rowptr: torch.Tensor    # int32 (n_rows + 1,), absolute offsets
@@ -1410,7 +1410,7 @@ def _sk_args(csr: KLCSR, F3: torch.Tensor, S3: torch.Tensor, st: torch.Tensor | 
     if csr.n_rows != Lf or csr.n_cols != Ls or csr.rowptr.dtype != torch.int32:
         raise ValueError(f"CSR {csr.n_rows} x {csr.n_cols} does not match fixed {Lf} x "
                          f"streamed {Ls}")
-    _native_dtype_k("sparse KL", F3.dtype, K, 64)
+    _native_dtype_k("sparse KL", F3.dtype, K, 128)
     for name, t in (("F3", F3), ("S3", S3)):
         _bp_check(name, t, F3.device)
     if st is None:
@@ -1430,7 +1430,8 @@ def kl_sparse_h_block(csr: KLCSR, HT3: torch.Tensor, W3: torch.Tensor, eps: floa
                       xsum: float | None = None) -> None:
     """:func:`beta_h_block` at beta = 1 over the CSR rows ``csr`` (cells x genes) of X:
     ``nsteps`` fused KL MU steps of HT3 (R, K, c) in place against W3 (R, K, G), the same
-    on-device stopping rule (sparse_kl.hip side 0).  ``st``: :func:`kl_st` of W3."""
+    on-device stopping rule (side 0 of sparse_kl.hip, sparse_kl_wide.hip above K = 32,
+    sparse_kl_xwide.hip above K = 64; K <= 128).  ``st``: :func:`kl_st` of W3."""
     R, K, N = HT3.shape
     if tol is not None and act is None:
         raise ValueError("the stopping rule needs an act array")
@@ -1486,7 +1487,8 @@ def kl_sparse_w_num(tiles: list, HT3: torch.Tensor, W3: torch.Tensor, eps: float
                     st: torch.Tensor | None = None) -> torch.Tensor:
     """KL spectra numerators num = HT Q over a row chunk given as :func:`kl_csr_tiles`
     (cells tiled so that each tile's usages fit in LDS), as (tiles, R, K, G) partials -- the
-    :func:`beta_w_partials` layout (sparse_kl.hip side 1).  ``st``: :func:`kl_st` of HT3."""
+    :func:`beta_w_partials` layout (side 1 of sparse_kl.hip, sparse_kl_wide.hip above K = 32,
+    sparse_kl_xwide.hip above K = 64; K <= 128).  ``st``: :func:`kl_st` of HT3."""
     R, K, c = HT3.shape
     G = W3.shape[2]
     _require_native()

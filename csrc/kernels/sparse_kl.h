@@ -1,5 +1,6 @@
 // Shared pieces of the sparse KL kernels (sparse_kl.hip: K <= 32, sparse_kl_wide.hip:
-// 33 <= K <= 64): launch parameters, the DPP helper and the stopping-rule tail.
+// 33 <= K <= 64, sparse_kl_xwide.hip: 65 <= K <= 128): launch parameters, the DPP helper
+// and the stopping-rule tail.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,7 +16,8 @@ constexpr int kSkRow = 16;                      // lanes per fixed column (one D
 constexpr int kSkCols = kSkThreads / kSkRow;    // columns in flight per workgroup
 constexpr int kSkLdsBytes = 128 * 1024;         // LDS budget for the staged S^T rows
 constexpr int kSkMaxK = 32;                     // sk_kernel; above it sk_wide_kernel
-constexpr int kSkWideMaxK = 64;
+constexpr int kSkWideMaxK = 64;                 // sk_wide_kernel; above it sk_xwide_kernel
+constexpr int kSkXWideMaxK = 128;
 
 struct SkParams {
   const int* rowptr;   // (Lf + 1): fixed column i owns entries [rowptr[i], rowptr[i+1])
@@ -118,5 +120,7 @@ __device__ __forceinline__ void sk_tail(const SkParams& p, int rep, int grp, flo
 
 // sparse_kl_wide.hip: 33 <= K <= 64, same parameters and launch geometry as sk_kernel
 hipError_t sk_wide_run(int side, const SkParams& p, hipStream_t s);
+// sparse_kl_xwide.hip: 65 <= K <= 128, likewise
+hipError_t sk_xwide_run(int side, const SkParams& p, hipStream_t s);
 
 }  // namespace cnmf

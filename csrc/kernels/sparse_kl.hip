@@ -19,8 +19,9 @@
 // usages in registers.  The block-objective stopping rule is the dense kernel's (last
 // workgroup of the replicate to arrive decides, cdna_hip_programming.md G16).
 //
-// This unit holds the K <= 32 kernel and the launcher for every K <= 64; 33 <= K <= 64 run
-// sparse_kl_wide.hip (components split over the lanes of a row), sparse_kl.h is shared.
+// This unit holds the K <= 32 kernel and the launcher for every K <= 128; 33 <= K <= 64 run
+// sparse_kl_wide.hip and 65 <= K <= 128 sparse_kl_xwide.hip (components split over the lanes
+// of a row), sparse_kl.h is shared.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -277,7 +278,7 @@ extern "C" hipError_t cnmf_sk_run(
     float l2, float tol, int conv_mode, double* hstate, double* part, int* counter, int* act,
     int* iters, const int* active, double* loss, double xsum, hipStream_t stream) {
   if (R <= 0 || Lf <= 0) return hipSuccess;
-  if (K < 1 || K > cnmf::kSkWideMaxK || (side != 0 && side != 1) || rowptr == nullptr ||
+  if (K < 1 || K > cnmf::kSkXWideMaxK || (side != 0 && side != 1) || rowptr == nullptr ||
       ST == nullptr || (reinterpret_cast<uintptr_t>(ST) & 15) != 0 || st_rs % 4 != 0)
     return hipErrorInvalidValue;
   cnmf::SkParams p;
@@ -293,16 +294,21 @@ extern "C" hipError_t cnmf_sk_run(
   p.den_vec = den_vec; p.l1 = l1; p.l2 = l2; p.tol = tol; p.conv_mode = conv_mode;
   p.hstate = hstate; p.part = part; p.counter = counter; p.act = act; p.iters = iters;
   p.active = active; p.loss = loss; p.xsum = xsum;
-  const bool wide = K > cnmf::kSkMaxK;   // sparse_kl_wide.hip: components split over lanes
+  // above kSkMaxK the components are split over lanes: sparse_kl_wide.hip, sparse_kl_xwide.hip
+  const bool wide = K > cnmf::kSkMaxK, xwide = K > cnmf::kSkWideMaxK;
   if (side == 1) {
     if (num == nullptr) return hipErrorInvalidValue;
-    return wide ? cnmf::sk_wide_run(1, p, stream) : cnmf::sk_launch_u<false>(p, stream);
+    return xwide  ? cnmf::sk_xwide_run(1, p, stream)
+           : wide ? cnmf::sk_wide_run(1, p, stream)
+                  : cnmf::sk_launch_u<false>(p, stream);
   }
   if (nsteps < 0 || den_vec == nullptr || (part != nullptr && (counter == nullptr || act == nullptr)) ||
       (part != nullptr && conv_mode == 1 && hstate == nullptr) ||
       (nsteps == 0 && loss == nullptr && part == nullptr))
     return hipErrorInvalidValue;
-  return wide ? cnmf::sk_wide_run(0, p, stream) : cnmf::sk_launch_u<true>(p, stream);
+  return xwide  ? cnmf::sk_xwide_run(0, p, stream)
+         : wide ? cnmf::sk_wide_run(0, p, stream)
+                : cnmf::sk_launch_u<true>(p, stream);
 }
 
 extern "C" int cnmf_sk_groups(int Lf, int R, int Ls, int K) {
