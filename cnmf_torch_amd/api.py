@@ -43,7 +43,7 @@ from .models.consensus import (cluster_medians, kmeans, l2_normalize_rows, local
                                pairwise_distances, silhouette)
 from .models.hvg import (compute_tpm, exact_mean_var, get_highvar_genes,
                          get_highvar_genes_sparse, get_mean_var)
-from .models.nmf import NMFBatchSolver, NMFOptions
+from .models.nmf import NMFBatchSolver, NMFOptions, SparseTilesX
 from . import ops
 from .models.ols import efficient_ols_all_cols
 from .models.pp import scale as pp_scale
@@ -847,8 +847,14 @@ class cNMF:
         return res.spectra(0).cpu().numpy(), res.usages(0).cpu().numpy()
 
     def factorize(self, worker_i=0, total_workers=1, skip_completed_runs=False, device=None,
-                  replicate_batch: int | None = None, save_usages: bool = False, verbose=True):
+                  replicate_batch: int | None = None, save_usages: bool = False, verbose=True,
+                  x_storage: str | None = None):
         """Run this worker's share of the replicate ledger (cnmf.py:839-892).
+
+        ``x_storage``: "dense" (default; the resident fp32 matrix and its bf16 planes) or
+        "tiles" (the matrix held once as tiles of its non-zeros, models.nmf.SparseTilesX:
+        no dense copy on host or device; online Frobenius MU / HALS with random init
+        only).  None: $CNMF_X_STORAGE, else "dense".
 
         Jobs with the same K are solved together in batches of ``replicate_batch``
         replicates (default: all of them that fit the device memory budget).
@@ -868,12 +874,12 @@ class cNMF:
             jobs = list(worker_filter(list(run_params.index[~done]), worker_i, total_workers))
         self.factorize_jobs(jobs, worker_label=worker_i, device=device,
                             replicate_batch=replicate_batch, save_usages=save_usages,
-                            verbose=verbose, run_params=run_params)
+                            verbose=verbose, run_params=run_params, x_storage=x_storage)
 
     def factorize_jobs(self, jobs, worker_label=0, device=None, replicate_batch=None,
                        save_usages=False, verbose=True, run_params=None, comm=None,
-                       row_range=None, row_segments=None, collect=None):
-        """Factorise an explicit list of ledger rows.
+                       row_range=None, row_segments=None, collect=None, x_storage=None):
+        """Factorise an explicit list of ledger rows (``x_storage``: see :meth:`factorize`).
 
         ``collect`` (a dict): also keep every written replicate's spectra in memory,
         ``collect[(k, iter)] = (k x G) float32``, plus ``collect["genes"]`` -- for the
@@ -888,6 +894,13 @@ class cNMF:
             run_params = load_df_from_npz(self.paths["nmf_replicate_parameters"])
         if not jobs:
             return
+        x_storage = x_storage or os.environ.get("CNMF_X_STORAGE") or "dense"
+        if x_storage not in ("dense", "tiles"):
+            raise ValueError(f"x_storage {x_storage!r}: 'dense' or 'tiles'")
+        if x_storage == "tiles" and (row_range is not None or row_segments is not None
+                                     or (comm is not None and comm.world_size > 1)):
+            raise ValueError("SparseTilesX (x_storage='tiles'): the cell-sharded multi-GPU "
+                             "route is not supported on tile storage")
         if row_range is not None and row_segments is None:
             row_segments = [tuple(int(v) for v in row_range)]
             contiguous = True
@@ -900,7 +913,15 @@ class cNMF:
                 torch.set_num_threads(max(1, int(kwargs["n_jobs"])))
             row_map = schedule = None
             Xd = None
-            if row_segments is None:
+            if x_storage == "tiles":
+                # the file's matrix (scipy CSR, or dense on disk) straight into the tile
+                # holder, row block by row block: no resident mirror, no _dense32
+                norm_counts = read_h5ad(self.paths["normalized_counts"])
+                Xd = SparseTilesX.from_scipy(norm_counts.X, device=dev)
+                norm_counts.X = None
+                Xh = None
+                cell_idx = np.arange(norm_counts.shape[0])
+            elif row_segments is None:
                 norm_counts = self._read_norm_counts(dev, factorize=True)
                 Xd = _resident_X(norm_counts, dev) if norm_counts.X is None else None
                 Xh = norm_counts.X
@@ -1038,7 +1059,7 @@ class cNMF:
             _flush()
             pool.shutdown()
 
-    def _job_batches(self, X: torch.Tensor, jobs, nc, dev, replicate_batch, comm, mixed):
+    def _job_batches(self, X, jobs, nc, dev, replicate_batch, comm, mixed):
         """Consecutive runs of the K-sorted ``jobs`` solved as one batch each: up to
         ``replicate_batch`` replicates, within ~40 % of free device memory, and (unless
         ``mixed``) of a single K.  Identical on every rank under DP."""

@@ -7,7 +7,7 @@ commented out at cnmf.py:1430) and gives ``--total-workers`` its documented mean
 shards the ledger over ranks automatically, one rank per GPU.
 
 Additions: ``--algo``/``--mode`` (prepare), ``--replicate-batch``, ``--device``,
-``--save-usages`` (factorize), ``--kmeans-backend``, ``--no-build-reference``
+``--save-usages``, ``--x-storage`` (factorize), ``--kmeans-backend``, ``--no-build-reference``
 (consensus), ``--skip-missing-files`` (combine).
 """
 from __future__ import annotations
@@ -63,6 +63,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--replicate-batch", type=int, default=None,
                    help="[factorize] Replicates solved together per launch (default: auto)")
     p.add_argument("--device", type=str, default=None, help="[factorize/consensus] torch device override")
+    p.add_argument("--x-storage", type=str, default=None, choices=["dense", "tiles"],
+                   help="[factorize] how the normalised counts are held: dense (default) or "
+                        "tiles (64 x 64 tiles of the non-zeros, no dense copy on host or "
+                        "device; online Frobenius mu / hals with random init, one GPU per "
+                        "matrix). Default: $CNMF_X_STORAGE, else dense")
     p.add_argument("--dp", action="store_true", default=False,
                    help="[factorize] cell-sharded data parallelism under torchrun: every rank "
                         "holds a shard of the cells, all ranks solve every replicate with the "
@@ -120,6 +125,8 @@ def main(argv=None) -> int:
         obj.prepare(comm=comm, prewarm=False, **_prepare_kwargs(args))
     elif args.command == "factorize":
         world = int(os.environ.get("WORLD_SIZE", "1"))
+        if args.x_storage:      # every route below reads it (api.cNMF.factorize_jobs)
+            os.environ["CNMF_X_STORAGE"] = args.x_storage
         if args.dp:
             from .parallel.runner import dp_factorize
 
@@ -137,7 +144,8 @@ def main(argv=None) -> int:
             tw = args.total_workers if (args.worker_index is not None and args.total_workers > 0) else 1
             obj.factorize(worker_i=wi, total_workers=tw,
                           skip_completed_runs=args.skip_completed_runs, device=args.device,
-                          replicate_batch=args.replicate_batch, save_usages=args.save_usages)
+                          replicate_batch=args.replicate_batch, save_usages=args.save_usages,
+                          x_storage=args.x_storage)
     elif args.command == "combine":
         obj.combine(components=args.components, skip_missing_files=args.skip_missing_files)
     elif args.command == "consensus":

@@ -59,6 +59,7 @@ from .nmf_base import (  # noqa: F401
     NMFOptions,
     NMFResult,
     PlanesOnlyX,
+    SparseTilesX,
     _FUSED_MAX_SLABS,
     _LAYOUT_REPLAY,
     _XPlanes,
@@ -124,17 +125,30 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
         self.schedule = schedule
         self.opts = opts
         self.comm = comm or LocalComm()
-        self._virtual = isinstance(X, PlanesOnlyX)
+        self._virtual = isinstance(X, (PlanesOnlyX, SparseTilesX))
         if self._virtual:
-            # planes only: X stands in as a NaN-valued (N, G) view of one element -- shape,
+            # planes (or tiles) only: X stands in as a NaN-valued (N, G) view of one element -- shape,
             # device and dtype for the bookkeeping; any read of its values would surface as
             # NaN errors, and every code path that reads X raises before it
             if beta_value(opts.beta_loss) != 2.0 or \
                     opts.mode != "online" or opts.online_stats != "pass" or \
                     opts.init != "random" or opts.algo not in ("mu", "hals") or \
                     opts.dtype != torch.float32:
-                raise ValueError("PlanesOnlyX supports online Frobenius MU/HALS with random "
-                                 "init in float32 (the planes are the only copy of X)")
+                name = type(X).__name__
+                bad = [f"{k}={v!r}" for k, v, ok in (
+                    ("beta_loss", opts.beta_loss, beta_value(opts.beta_loss) == 2.0),
+                    ("mode", opts.mode, opts.mode == "online"),
+                    ("online_stats", opts.online_stats, opts.online_stats == "pass"),
+                    ("init", opts.init, opts.init == "random"),
+                    ("algo", opts.algo, opts.algo in ("mu", "hals")),
+                    ("dtype", opts.dtype, opts.dtype == torch.float32)) if not ok]
+                raise ValueError(f"{name} supports online Frobenius MU/HALS with random "
+                                 f"init in float32 (it is the only copy of X); got "
+                                 + ", ".join(bad))
+            if isinstance(X, SparseTilesX) and (self.comm.is_distributed or row_map is not None):
+                raise ValueError("SparseTilesX: the cell-sharded multi-GPU route is not "
+                                 "supported on tile storage")
+            self._holder = type(X).__name__
             src = X
             X = torch.full((1, 1), float("nan"), device=src.device).expand(*src.shape)
         self.X = X if X.dtype == opts.dtype else X.to(opts.dtype)
@@ -153,7 +167,7 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
         self._ws_reserve = 0        # bytes of per-batch workspaces still to allocate (run)
         if self._virtual:
             local_sq = src.x_sq
-            self._xp = src.planes
+            self._xp = src if isinstance(src, SparseTilesX) else src.planes
             self._mean_x = self.comm.allreduce_scalar(src.sum) / max(
                 self.comm.allreduce_scalar(float(src.shape[0] * src.shape[1])), 1.0)
         elif self.X.device.type == "cuda" and self.X.dtype == torch.float32 and self.X.numel():
@@ -391,6 +405,9 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
             self._need_x("the numerator GEMM without planes")
             return W @ self.X[a:b].t()
         out = torch.empty((W.shape[0], b - a), device=W.device, dtype=W.dtype)
+        if isinstance(xp, SparseTilesX):
+            ops.gemm_tiles(out, wpl[:ops.gemm_a_planes(xp.Gp)], xp.tiles, "n", a, b, W.shape[0])
+            return out
         ops.gemm_planes(out, wpl[:ops.gemm_a_planes(xp.Gp)], xp.x[:, a:], W.shape[0], b - a,
                         xp.Gp)
         return out
@@ -410,12 +427,16 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
         hpl = self._plane_buf("h", HT.shape[0], kd)
         if not presplit:
             ops.split_planes(HT[:, a:b], hpl[:, :HT.shape[0]])
+        if isinstance(xp, SparseTilesX):
+            ops.gemm_tiles(B, hpl[:ops.gemm_a_planes(kd)], xp.tiles, "s", a, b, HT.shape[0],
+                           accumulate=accumulate, col_scale=xp.unit)
+            return
         ops.gemm_planes(B, hpl[:ops.gemm_a_planes(kd)], xp.xt[:, :, a:], HT.shape[0], xp.G, kd,
                         accumulate=accumulate, col_scale=xp.unit)
 
     def _need_x(self, what: str) -> None:
         if self._virtual:
-            raise ValueError(f"PlanesOnlyX: {what} needs the fp32 matrix, which is not held "
+            raise ValueError(f"{self._holder}: {what} needs the fp32 matrix, which is not held "
                              "(online chunk starts must be multiples of 8)")
 
     def _mean(self) -> float:
@@ -568,8 +589,8 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
                 or ops._ENV["CNMF_SOLVE_PIPE"] == "0" or o.algo != "mu"
                 or o.online_stats != "pass" or o.online_inner_conv != "loss"
                 or any(v != 0.0 for v in (o.l1_H, o.l2_H, o.l1_W, o.l2_W))
-                or self._planes() is None):
-            return False
+                or self._planes() is None or isinstance(self._xp, SparseTilesX)):
+            return False      # (the fused step reads the dense plane layouts xp.x / xp.xt)
         if dp:
             # the reduce-scattered W-solve partitions the replicates of every K group of
             # the batch over the ranks (mixed-K batches: one packed exchange per group)

@@ -615,6 +615,140 @@ class PlanesOnlyX:
 
 
 
+class SparseTilesX:
+    """A cells x genes matrix held on the device ONCE, as 64 x 64 tiles of its non-zeros
+    (ops.XTiles; csrc/kernels/gemm_tiles.hip), plus its statistics -- about 4 bytes per
+    non-zero at one value plane instead of the >= 4 bytes per ENTRY of the two dense plane
+    layouts of :class:`_XPlanes`.  Value semantics are _XPlanes's: count data (a per-gene
+    ``unit``, _count_units) is stored as its integer count matrix in ``pb`` = 1 plane
+    (counts <= 256) or 2 (< 65536) with the unit folded into the other operand / the output
+    columns, other data as _float_planes(G) planes of X itself.  Built block by block from
+    a :class:`RowBlocks` source whose block starts are multiples of 64 (the tile height):
+    neither the host nor the device ever holds the dense matrix.  ``NMFBatchSolver`` takes
+    it in place of X under :class:`PlanesOnlyX`'s restrictions."""
+
+    TILE = 64
+
+    def __init__(self, src: RowBlocks):
+        self.shape, self.device, self.dtype = src.shape, src.device, torch.float32
+        N, G = self.shape
+        T = self.TILE
+        dev = self.device
+        mn, sq, neg, sm = _block_colstats(src)
+        self.x_sq = float(sq.sum())
+        self.sum = float(sm.sum())
+        unit = _count_units(src, stats=(mn, sq, neg))
+        if unit is not None:
+            cmax = 0.0
+            for _, blk in src.blocks():
+                if blk.numel():
+                    cmax = max(cmax, float(torch.round(blk / unit).max()))
+            pb = 1 if cmax <= 256 else 2
+            if cmax >= 65536:
+                unit, pb = None, _XPlanes._float_planes(G)
+        else:
+            pb = _XPlanes._float_planes(G)
+        self.unit, self.pb = unit, pb
+        self.N, self.G = N, G
+        self.Gp = -(-G // T) * T
+        ntr, ntg = -(-N // T), -(-G // T)
+        counts = torch.zeros(ntr * ntg, dtype=torch.int64, device=dev)
+        ents, extras = [], [[] for _ in range(pb - 1)]
+        for a, blk in src.blocks():
+            if a % T:
+                raise ValueError(f"SparseTilesX: block start {a} is not a multiple of {T}")
+            C = torch.round(blk / unit) if unit is not None else blk
+            nz = C.nonzero()
+            if nz.shape[0] == 0:
+                continue
+            r, c = nz[:, 0], nz[:, 1]
+            vals = C[r, c].contiguous()
+            r = r + a
+            key = torch.div(r, T, rounding_mode="floor") * ntg + \
+                torch.div(c, T, rounding_mode="floor")
+            order = torch.argsort(key, stable=True)
+            counts += torch.bincount(key, minlength=ntr * ntg)
+            n4 = -(-vals.numel() // 4) * 4
+            pl = torch.zeros((pb, 1, n4), dtype=torch.int16, device=dev)
+            ops.split_planes(vals.view(1, -1), pl)
+            pl = pl[:, 0, :vals.numel()].index_select(1, order)
+            word = (pl[0].to(torch.int64) & 0xFFFF) | ((c[order] % T) << 16) | \
+                ((r[order] % T) << 22)
+            ents.append(word.to(torch.int32))          # < 2^28: no wrap
+            for p in range(1, pb):
+                extras[p - 1].append(pl[p].contiguous())
+            del C, nz, r, c, vals, key, order, pl, word
+        nnz = int(sum(e.numel() for e in ents))
+
+        def cat(parts, dtype):       # >= 1 element, so the kernel's clamped loads are valid
+            return torch.cat(parts) if parts else torch.zeros(1, dtype=dtype, device=dev)
+
+        ptr = torch.zeros(ntr * ntg + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        self.tiles = ops.XTiles(cat(ents, torch.int32),
+                                tuple(cat(x, torch.int16) for x in extras), ptr, nnz, N, G)
+        self.nnz = nnz
+        self._validate()
+
+    def _validate(self) -> None:
+        """A malformed entry would become an out-of-tile LDS write or a read past the
+        arrays in the kernel: pointers monotone and ending at the entry count, local
+        coordinates inside the real extent of their tile (checked in bands of row tiles)."""
+        t = self.tiles
+        T = self.TILE
+        ntr, ntg = -(-self.N // T), -(-self.G // T)
+        ok = int(t.ptr[0]) == 0 and int(t.ptr[-1]) == t.nnz and t.ptr.numel() == ntr * ntg + 1
+        ok = ok and bool((torch.diff(t.ptr) >= 0).all()) and t.ent.numel() >= max(t.nnz, 1) \
+            and all(x.numel() >= max(t.nnz, 1) for x in t.extra)
+        band = 1024                                        # row tiles per check
+        edges = t.ptr[::ntg * band].tolist() + [t.nnz]
+        for i in range(len(edges) - 1):
+            if not ok or edges[i + 1] == edges[i]:
+                continue
+            t0 = i * band * ntg
+            t1 = min(t0 + band * ntg, ntr * ntg)
+            e = t.ent[edges[i]:edges[i + 1]].to(torch.int64) & 0xFFFFFFFF
+            tid = torch.repeat_interleave(torch.arange(t0, t1, device=e.device),
+                                          torch.diff(t.ptr[t0:t1 + 1]))
+            row = torch.div(tid, ntg, rounding_mode="floor") * T + ((e >> 22) & 63)
+            col = (tid % ntg) * T + ((e >> 16) & 63)
+            ok = bool(((row < self.N) & (col < self.G) & ((e >> 28) == 0)).all())
+        if not ok:
+            raise RuntimeError("SparseTilesX: the tile structure failed its consistency check")
+
+    @classmethod
+    def from_scipy(cls, csr, device="cpu", rows: int = 1 << 16) -> "SparseTilesX":
+        """From a scipy sparse (or dense numpy) cells x genes matrix: row slices of
+        ``rows`` cells are densified one at a time and uploaded."""
+        N, G = csr.shape
+        rows = max(cls.TILE, rows // cls.TILE * cls.TILE)
+        if hasattr(csr, "tocsr"):
+            csr = csr.tocsr()
+
+        def blocks():
+            for a in range(0, N, rows):
+                sl = csr[a:a + rows]
+                sl = sl.toarray() if hasattr(sl, "toarray") else np.asarray(sl)
+                yield a, torch.from_numpy(np.ascontiguousarray(sl, dtype=np.float32)).to(device)
+
+        return cls(RowBlocks(N, G, blocks, device))
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes held: entries, further value planes, tile pointers, unit."""
+        t = self.tiles
+        ts = [t.ent, t.ptr, *t.extra] + ([self.unit] if self.unit is not None else [])
+        return int(sum(x.numel() * x.element_size() for x in ts))
+
+    def to_dense(self) -> torch.Tensor:
+        """The float32 matrix the tiles stand for (tests): the sum of the value planes,
+        times the unit for count data."""
+        pl = ops.reference.planes_to_f64(ops.reference.tiles_to_planes(self.tiles))
+        X = pl.sum(0).to(torch.float32)
+        return X * self.unit if self.unit is not None else X
+
+
+
 def kernel_max_rank(beta: float, algo: str) -> int | None:
     """Largest K the native kernels factorise (None: no limit).  Frobenius MU: any K --
     register-tiled kernels up to 128 (padded, native_rank), the rank-general solve beyond

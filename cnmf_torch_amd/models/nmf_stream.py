@@ -47,7 +47,9 @@ class _StreamMixin:
                 and o.online_stats == "pass" and o.online_inner_conv == "loss"
                 and o.init == "random" and not self.comm.is_distributed
                 and all(v == 0.0 for v in (o.l1_H, o.l2_H, o.l1_W, o.l2_W))
-                and int(np.max(ks)) <= 32 and not ops.eager_active())
+                and int(np.max(ks)) <= 32 and not ops.eager_active()
+                # continuous batching rides the fused step, which tile storage does not take
+                and type(self._xp).__name__ != "SparseTilesX")
 
     def run_stream(self, seeds, ks=None, live=None, keep_usages: bool = True,
                    on_result=None) -> NMFResult:

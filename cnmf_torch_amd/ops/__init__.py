@@ -2294,6 +2294,76 @@ def _gate_ptr(gate, dev) -> int:
     return gate.data_ptr()
 
 
+class XTiles(NamedTuple):
+    """A sparse cells x genes matrix as 64 x 64 tiles of its non-zeros (gemm_tiles.hip; built
+    and checked by models.nmf_base.SparseTilesX).  ``ent`` (int32, max(nnz, 1)): per entry
+    the bf16 pattern of value plane 0 in bits 0-15, the local gene in bits 16-21 and the
+    local cell in bits 22-27; ``extra``: one int16 tensor per further value plane, parallel
+    to ``ent``; ``ptr`` (int64, tiles + 1): entry offsets of the tiles, row-tile major."""
+    ent: torch.Tensor
+    extra: tuple
+    ptr: torch.Tensor
+    nnz: int
+    N: int
+    G: int
+
+    @property
+    def pb(self) -> int:
+        return 1 + len(self.extra)
+
+
+def gemm_tiles(C: torch.Tensor, A: torch.Tensor, tiles: XTiles, side: str, r0: int, r1: int,
+               M: int, accumulate: bool = False, col_scale: torch.Tensor | None = None,
+               gate: torch.Tensor | None = None) -> None:
+    """The product contract of :func:`gemm_planes` (sum over plane pairs i + j <= 2, A as 2
+    or 3 int16 planes) with the data matrix X held as ``tiles`` (gemm_tiles.hip):
+
+    side "n":  C[:M, :r1-r0] (+)= (A . X[r0:r1, :]^T) * col_scale   A's k = gene (>= Gp deep)
+    side "s":  C[:M, :G]     (+)= (A . X[r0:r1, :]) * col_scale     A's k = cell - r0
+                                                         (>= r1 - r0 padded to planes_bk)
+
+    A's k range beyond the genes / the cells of the range must hold zeros.  One workgroup
+    sums an output tile's k-steps in order: repeatable bit for bit.  ``gate`` as in
+    gemm_planes."""
+    if side not in ("n", "s"):
+        raise ValueError(f"gemm_tiles: side {side!r} (n or s)")
+    pa, a_rows, a_k = A.shape
+    r0, r1, M = int(r0), int(r1), int(M)
+    if not 0 <= r0 <= r1 <= tiles.N:
+        raise ValueError(f"gemm_tiles: rows [{r0}, {r1}) of {tiles.N}")
+    ncol = r1 - r0 if side == "n" else tiles.G
+    kd = -(-tiles.G // 64) * 64 if side == "n" else -(-(r1 - r0) // 64) * 64
+    if A.dtype != torch.int16 or A.stride(2) != 1 or A.stride(1) % 8 or A.stride(0) % 8 \
+            or A.data_ptr() % 16:
+        raise ValueError("A: int16 planes with unit k stride, 8-aligned strides, 16-byte base")
+    if not 2 <= pa <= 3 or M > a_rows or a_k < kd:
+        raise ValueError(f"gemm_tiles: planes {pa}, M {M}/{a_rows}, k extent {a_k} < {kd}")
+    if C.dtype != torch.float32 or C.stride(1) != 1 or C.shape[0] < M or C.shape[1] < ncol:
+        raise ValueError("C: float32 (>= M, >= columns) with unit column stride required")
+    if col_scale is not None and (col_scale.dtype != torch.float32 or col_scale.numel() < ncol
+                                  or not col_scale.is_contiguous()):
+        raise ValueError("col_scale: contiguous float32 with one entry per output column")
+    if M <= 0 or r1 <= r0:
+        return
+    if not use_native(C):
+        prod = reference.gemm_tiles(A[:, :M], tiles, side, r0, r1)
+        if col_scale is not None:
+            prod = prod * col_scale[:ncol].double()
+        if accumulate:
+            C[:M, :ncol] += prod.to(C.dtype)
+        else:
+            C[:M, :ncol] = prod.to(C.dtype)
+        return
+    ex = tiles.extra
+    _hip.gemm_tiles(A.data_ptr(), A.stride(1), A.stride(0), a_rows, a_k, tiles.ent.data_ptr(),
+                    ex[0].data_ptr() if len(ex) > 0 else 0,
+                    ex[1].data_ptr() if len(ex) > 1 else 0, tiles.ptr.data_ptr(),
+                    int(tiles.nnz), tiles.N, tiles.G, C.data_ptr(), C.stride(0),
+                    int(C.shape[1]), col_scale.data_ptr() if col_scale is not None else 0, M,
+                    0 if side == "n" else 1, r0, r1, pa, tiles.pb, int(bool(accumulate)),
+                    _gate_ptr(gate, C.device), _stream_ptr(C))
+
+
 def gemm_stages(variant: int) -> int:
     """LDS pipeline depth of the split GEMM (k-steps in flight + 1; the kernel drops to 2
     where 3 stages would not fit in LDS).  Measured on MI355X

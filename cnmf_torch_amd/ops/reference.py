@@ -355,6 +355,43 @@ def gemm_planes(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def tiles_to_planes(tiles, r0: int = 0, r1: int | None = None) -> torch.Tensor:
+    """(pb, r1 - r0, G) int16 bf16 planes of rows [r0, r1) of an ops.XTiles matrix."""
+    r1 = tiles.N if r1 is None else r1
+    ntg = -(-tiles.G // 64)
+    t0, t1 = r0 // 64, -(-r1 // 64)                    # row tiles the range touches
+    ptr = tiles.ptr[t0 * ntg:t1 * ntg + 1]
+    e0, e1 = (int(ptr[0]), int(ptr[-1])) if r1 > r0 else (0, 0)
+    ent = tiles.ent[e0:e1].to(torch.int64) & 0xFFFFFFFF
+    tid = torch.repeat_interleave(torch.arange(t0 * ntg, t1 * ntg, device=ent.device),
+                                  torch.diff(ptr)) if e1 > e0 else ent
+    row = torch.div(tid, ntg, rounding_mode="floor") * 64 + ((ent >> 22) & 63)
+    col = (tid % ntg) * 64 + ((ent >> 16) & 63)
+    keep = (row >= r0) & (row < r1)
+    out = torch.zeros((tiles.pb, r1 - r0, tiles.G), dtype=torch.int16, device=ent.device)
+    vals = [(ent & 0xFFFF).to(torch.int32)] + [x[e0:e1].to(torch.int32) & 0xFFFF
+                                               for x in tiles.extra]
+    for p, v in enumerate(vals):
+        v16 = torch.where(v >= 32768, v - 65536, v).to(torch.int16)
+        out[p].index_put_((row[keep] - r0, col[keep]), v16[keep])
+    return out
+
+
+def gemm_tiles(A: torch.Tensor, tiles, side: str, r0: int, r1: int) -> torch.Tensor:
+    """Oracle of ops.gemm_tiles in float64: the tiles' rows [r0, r1) densified, then the
+    plane-pair sum of gemm_planes.  A: (pa, M, k) int16 planes."""
+    Xf = planes_to_f64(tiles_to_planes(tiles, r0, r1))          # (pb, rows, G)
+    Af = planes_to_f64(A)
+    n = r1 - r0
+    out = torch.zeros((A.shape[1], n if side == "n" else tiles.G), dtype=torch.float64,
+                      device=A.device)
+    for i in range(A.shape[0]):
+        for j in range(Xf.shape[0]):
+            if i + j <= 2:
+                out += Af[i][:, :tiles.G] @ Xf[j].t() if side == "n" else Af[i][:, :n] @ Xf[j]
+    return out
+
+
 def colstats(X: torch.Tensor):
     inf = torch.tensor(float("inf"), dtype=X.dtype, device=X.device)
     mn = torch.where(X > 0, X, inf).amin(0) if X.shape[0] else \

@@ -538,6 +538,21 @@ PYBIND11_MODULE(_hip, m) {
                 "cnmf_split_planes");
         });
 
+  m.def("gemm_tiles",
+        [](uintptr_t A, long long lda, long long a_plane, int a_rows, int a_k, uintptr_t ent,
+           uintptr_t v1, uintptr_t v2, uintptr_t tile_ptr, long long nnz, int n_cells,
+           int n_genes, uintptr_t C, long long ldc, int c_cols, uintptr_t col_scale, int M,
+           int side, int r0, int r1, int pa, int pb, int accumulate, uintptr_t gate,
+           uintptr_t stream) {
+          check(cnmf_gemm_tiles(P<const unsigned short>(A), lda, a_plane, a_rows, a_k,
+                                P<const unsigned>(ent), P<const unsigned short>(v1),
+                                P<const unsigned short>(v2), P<const long long>(tile_ptr), nnz,
+                                n_cells, n_genes, P<float>(C), ldc, c_cols,
+                                P<const float>(col_scale), M, side, r0, r1, pa, pb, accumulate,
+                                P<const int>(gate), reinterpret_cast<hipStream_t>(stream)),
+                "cnmf_gemm_tiles");
+        });
+
   m.def("colstats_blocks", [](int N) { return cnmf_colstats_blocks(N); });
   m.def("colstats",
         [](uintptr_t X, long long ldx, int N, int G, uintptr_t pmin, uintptr_t psq,

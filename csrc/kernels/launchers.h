@@ -228,6 +228,13 @@ hipError_t cnmf_split_planes(const float* S, long long lds, int rows, int cols, 
                              const float* col_mul, unsigned short* P, long long ldp,
                              long long plane, int nplanes, hipStream_t stream);
 
+hipError_t cnmf_gemm_tiles(const unsigned short* A, long long lda, long long a_plane, int a_rows,
+                           int a_k, const unsigned* ent, const unsigned short* v1,
+                           const unsigned short* v2, const long long* tile_ptr, long long nnz,
+                           int n_cells, int n_genes, float* C, long long ldc, int c_cols,
+                           const float* col_scale, int M, int side, int r0, int r1, int pa,
+                           int pb, int accumulate, const int* gate, hipStream_t stream);
+
 int cnmf_colstats_blocks(int N);
 hipError_t cnmf_colstats(const float* X, long long ldx, int N, int G, float* pmin, double* psq,
                          int* pneg, float* mn, double* sq, int* neg, hipStream_t stream);

@@ -86,11 +86,12 @@ def device_counts(N, G, P, r0, r1, dev, comm, seed=0):
     return X
 
 
-def planes_only_counts(N, G, P, r0, r1, dev, comm, seed=0):
-    """The same matrix as device_counts, held ONLY as split-GEMM planes (nmf.PlanesOnlyX):
-    a statistics pass for the per-gene scale, then every planes pass regenerates the
-    blocks -- the 200 GB fp32 matrix of 10M x 5k is never resident."""
-    from cnmf_torch_amd.models.nmf import PlanesOnlyX, RowBlocks
+def planes_only_counts(N, G, P, r0, r1, dev, comm, seed=0, tiles=False):
+    """The same matrix as device_counts, held ONLY as split-GEMM planes (nmf.PlanesOnlyX)
+    or, ``tiles``, as tiles of its non-zeros (nmf.SparseTilesX): a statistics pass for the
+    per-gene scale, then every builder pass regenerates the blocks -- the 200 GB fp32
+    matrix of 10M x 5k is never resident."""
+    from cnmf_torch_amd.models.nmf import PlanesOnlyX, RowBlocks, SparseTilesX
 
     S = _programs(G, P, dev, seed)
     b0, b1 = r0 // BLOCK, (r1 + BLOCK - 1) // BLOCK
@@ -111,7 +112,7 @@ def planes_only_counts(N, G, P, r0, r1, dev, comm, seed=0):
         for b in range(b0, b1):
             lo, hi = max(r0, b * BLOCK), min(r1, (b + 1) * BLOCK)
             yield lo - r0, _count_block(S, b, dev, seed)[lo - b * BLOCK:hi - b * BLOCK] / sd
-    return PlanesOnlyX(RowBlocks(r1 - r0, G, blocks, dev))
+    return (SparseTilesX if tiles else PlanesOnlyX)(RowBlocks(r1 - r0, G, blocks, dev))
 
 
 def main():
@@ -137,7 +138,14 @@ def main():
     ap.add_argument("--planes-only", action="store_true",
                     help="hold X only as split-GEMM planes (10M x 5k on one GPU: fp32 X "
                          "and its planes do not fit together)")
+    ap.add_argument("--x-storage", choices=["dense", "planes", "tiles"], default=None,
+                    help="dense (fp32 + planes, the default), planes (= --planes-only) or "
+                         "tiles (the matrix held once as 64 x 64 tiles of its non-zeros, "
+                         "nmf.SparseTilesX; one process, no --dp)")
     a = ap.parse_args()
+    storage = a.x_storage or ("planes" if a.planes_only else "dense")
+    if storage == "tiles" and a.dp:
+        ap.error("--x-storage tiles: the cell-sharded route is not supported on tile storage")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -162,7 +170,10 @@ def main():
     else:
         r0, r1 = 0, N
     t0 = time.perf_counter()
-    X = (planes_only_counts if a.planes_only else device_counts)(N, G, a.k, r0, r1, dev, comm)
+    if storage == "dense":
+        X = device_counts(N, G, a.k, r0, r1, dev, comm)
+    else:
+        X = planes_only_counts(N, G, a.k, r0, r1, dev, comm, tiles=storage == "tiles")
     torch.cuda.synchronize()
     t_gen = time.perf_counter() - t0
     opts = NMFOptions(n_components=a.k, tol=1e-4, online_chunk_size=5000,
@@ -236,7 +247,10 @@ def main():
                                 "MB per step per rank not timed)") if emu else
                 f"{'dp' if a.dp else 'replicate'}x{world}",
                 "hbm_gb_X_per_gpu": round(N * G * 4 / 1e9 / (emu or (world if a.dp else 1)), 2),
-                "x_storage": "split-GEMM planes only" if a.planes_only else "fp32 + planes",
+                "x_storage": {"dense": "fp32 + planes", "planes": "split-GEMM planes only",
+                              "tiles": "tiles of the non-zeros"}[storage],
+                "x_nnz_fraction": round(X.nnz / (N * G), 4) if storage == "tiles" else None,
+                "x_holder_gb": round(X.nbytes / 1e9, 2) if storage == "tiles" else None,
                 "hbm_gb_peak": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)},
             "projection": proj,
             "data": "synthetic planted-program Poisson counts generated on device"}), flush=True)
