@@ -1307,7 +1307,10 @@ def beta_w_partials(X: torch.Tensor, XT: torch.Tensor | None, HT3: torch.Tensor,
     layout of :func:`beta_w_update` (beta_planes.hip side 1: HT streamed from its split-bf16
     panels, W3 the fixed operand, X read through its transpose ``XT`` (G, c)).  KL on fp16
     counts: ``xth`` (G, c) float16 with X^T == xth * unit per row, ``unit_inv`` = 1 / unit
-    (G,) -- read instead of XT (which may then be None)."""
+    (G,) -- read instead of XT (which may then be None).  With the fp16 KL numerator
+    (``CNMF_KL_FP16=1``) an element whose product HT^T W is exactly 0 is left out of Q
+    (beta_planes.h): num differs from the contract in entries (k, g) with W3[k, g] == 0
+    of such a gene, which :func:`beta_w_update` multiplies by W3[k, g]."""
     R, K, c = HT3.shape
     G = W3.shape[2]
     if X.shape != (c, G) or W3.shape[:2] != (R, K):

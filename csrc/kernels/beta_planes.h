@@ -45,6 +45,13 @@
 //   by 2^s, exactly), s = 0 to start with (x / P stays below ~200 on count data), and a
 //   step whose numerator comes out non-finite for some column is redone with that
 //   column's s raised by 12 (at most 6 times), so overflow never reaches the result.
+//   An element whose product is exactly 0 (a cell without usage, a gene without loading)
+//   has Q = x / eps in the contract; the fp16 plane drops it, since every h_k w_k of that
+//   element is 0 and it adds nothing to h_k num_k (usage update) or w_k num_k (spectra
+//   update), while as a Q it would overflow and cost the column's other terms their bits
+//   in the shift.  The spectra partials therefore differ from the contract in entries
+//   (k, g) with w_kg = 0 whose gene has such an element -- the update multiplies them by
+//   w_kg -- and nowhere else.
 //
 // The H-side kernel runs `nsteps` MU steps per launch: every workgroup's cells only
 // depend on their own usages and on W, so the steps need no cross-workgroup
@@ -490,10 +497,12 @@ bp_kernel(BpParams p) {
           }
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct) {
+            const float e0 = p.eps * csc[ct];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               const float x = xv[ct][e];
-              const float qv = x * __builtin_amdgcn_rcpf(e < 4 ? P0[ct][e] : P1[ct][e - 4]);
+              const float pv = e < 4 ? P0[ct][e] : P1[ct][e - 4];
+              const float qv = x * __builtin_amdgcn_rcpf(pv);
               if (kLoss) {
                 // x log2(x / p) with q' = q 2^-s: log2 q = log2 q' + s
                 const int j = j0 + (e >> 2) * 16 + 4 * q + (e & 3);
@@ -501,7 +510,10 @@ bp_kernel(BpParams p) {
                                         : 0.f;
                 lsum += (cok[ct] && j < p.Ls) ? t : 0.f;
               }
-              if (kNum) qh[ct][e] = (_Float16)qv;
+              // where the product is exactly 0 (P still equals its eps start) every h_k w_k
+              // is 0: x / eps adds nothing to h_k num_k (usages) or w_k num_k (spectra) --
+              // and as an fp16 Q it would overflow and shift the column's other terms away
+              if (kNum) qh[ct][e] = (_Float16)(pv == e0 ? 0.f : qv);
             }
             // the redo pass after an overflow saturates instead (x / p beyond 2^40)
             if (decltype(SAT)::value) qh[ct] = __builtin_elementwise_min(qh[ct], bp_h8(65504.f16));
