@@ -272,13 +272,16 @@ def solve(algo: str, x: torch.Tensor, numer: torch.Tensor, gram: torch.Tensor,
     gen_dev = (0, 0)
     if S > 1:
         epochs = (max_iter // max(1, check_every) + 3) if conv_mode == 1 else (max_iter + 2)
-        ws = _coop_workspace(x.device, _stream_ptr(x), R, epochs, S)
+        # granules per (replicate, epoch, slice): the pipelined solve exchanges
+        # (f, f0, lin, quad) at once (coop_sum4_tag_s), every other kernel two values
+        gran = COOP_GRANULES_PIPE if plan.kernel == "pipe" else 2
+        ws = _coop_workspace(x.device, _stream_ptr(x), R, epochs, S, gran)
         if coop_device_gen:
             gen = 0                         # unused: the kernel reads ws["gen_dev"]
         elif torch.cuda.is_current_stream_capturing():
             # a graph replays fixed arguments: zero this launch's granules in the graph
             # and tag them with a generation eager launches never reach
-            ws["slots"][: R * epochs * S * 2].zero_()
+            ws["slots"][: R * epochs * S * gran].zero_()
             gen = 0xFFFFFFFF
         else:
             ws["gen"] = ws["gen"] % 0x7FFFFFFE + 1   # tags this launch's arrivals (< 2^31)
@@ -392,6 +395,7 @@ _COOP_WS: dict = {}
 _COOP_RESIDENT: dict = {}
 COOP_COLS_PER_WG = 1024
 kCoopMaxSlices = 32          # solve_core.h: cooperative slices per replicate
+COOP_GRANULES_PIPE = 4       # solve_core.h coop_sum4_tag_s: the widest slot layout
 _TLS = threading.local()
 
 
@@ -614,14 +618,16 @@ def solve_plan(algo, K: int, n: int, nblocks: int, *, nsplit: int = 1, conv_mode
     return SolvePlan(kernel, max(S, nsplit), rpl, threads)
 
 
-def _coop_workspace(dev: torch.device, stream: int, R: int, epochs: int, S: int) -> dict:
-    """Per-(device, stream) scratch: {generation, value} granules [R*epochs*S*2] (int64,
-    zeroed once at allocation; coop_sum2 in csrc/kernels/solve_core.h), the launch
-    generation and the timeout flag.  Reused across launches on the same stream (stream
-    order serialises); the generation only grows, so granules need no re-zeroing."""
+def _coop_workspace(dev: torch.device, stream: int, R: int, epochs: int, S: int,
+                    gran: int = 2) -> dict:
+    """Per-(device, stream) scratch: {generation, value} granules [R*epochs*S*gran]
+    (int64, zeroed once at allocation; coop_sum2 / coop_sum4 in
+    csrc/kernels/solve_core.h), the launch generation and the timeout flag.  Reused across
+    launches on the same stream (stream order serialises), whatever their slot layout;
+    the generation only grows, so granules need no re-zeroing."""
     key = (str(dev), stream)
     ws = _COOP_WS.get(key)
-    need_slots = R * epochs * S * 2
+    need_slots = R * epochs * S * gran
     if ws is None or ws["slots"].numel() < need_slots:
         flag = ws["flag"] if ws is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         # device-side generation (solve_pipe.hip): tags from 2^31 up, never a host tag
@@ -646,7 +652,7 @@ def coop_reserve(dev: torch.device, stream: int, R: int, max_iter: int, check_ev
     workspace's zero-fill (and the reset of its device-side generation) into the graph
     and replay it every time."""
     epochs = max_iter // max(1, check_every) + 3
-    _coop_workspace(dev, stream, R, epochs, kCoopMaxSlices)
+    _coop_workspace(dev, stream, R, epochs, kCoopMaxSlices, COOP_GRANULES_PIPE)
 
 
 def coop_flags(device: torch.device | None = None) -> list:

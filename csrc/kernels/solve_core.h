@@ -35,7 +35,8 @@
 
 namespace cnmf {
 
-// cooperative slices per replicate (coop_sum2: one wave watches the 2 S granules)
+// cooperative slices per replicate (one wave watches the 2 S granules of coop_sum2, the
+// 4 S of coop_sum4)
 constexpr int kCoopMaxSlices = 32;
 
 template <int K>
@@ -213,6 +214,81 @@ __device__ __forceinline__ bool coop_sum2_tag_s(const SolveParams& p, unsigned g
   a = sred[0];
   b = sred[1];
   const bool good = sred[2] != 0.f;
+  __syncthreads();
+  return good;
+}
+
+// Four-value form of the exchange, for solve_pipe_kernel only: its slots are
+// [R][coop_epochs][S][4] granules (the host sizes and zeroes the workspace with that
+// stride for the "pipe" kernel; every other kernel keeps the two-value layout).  A check
+// publishes (f, f0, lin, quad) at once, so a solve that stops at that check already holds
+// the slice-ordered totals its epilogue would otherwise exchange a second time.  One wave
+// watches the 4 S granules, two per lane once S > 16.  Each value is summed in slice
+// order by its own lane: the same additions in the same order as coop_sum2_tag_s.
+// wait == false (uniform over the workgroup): publish only -- for the slices whose totals
+// nobody in the workgroup reads; nothing is returned in a..d then.
+__device__ __forceinline__ bool coop_sum4_tag_s(const SolveParams& p, unsigned gen, int rep,
+                                                int e, float& a, float& b, float& c, float& d,
+                                                float* sred, int S, int slice, bool wait) {
+  static_assert(4 * kCoopMaxSlices <= 128, "one wave watches two granules per lane");
+  if (S <= 1) return true;
+  if (e >= p.coop_epochs) {  // workspace too small: treat as timeout (host sizes it)
+    if (threadIdx.x == 0) atomicExch(p.coop_timeout, 2);
+    return false;
+  }
+  gran_t* g = (gran_t*)(p.coop_slots + (((long long)rep * p.coop_epochs + e) * S) * 4);
+  const unsigned long long tag = (unsigned long long)gen << 32;
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    if (lane < 4) {
+      const float mine = lane == 0 ? a : lane == 1 ? b : lane == 2 ? c : d;
+      __hip_atomic_store(g + 4 * slice + lane, tag | __float_as_uint(mine), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (wait) {
+      int ok = __builtin_amdgcn_readfirstlane(
+          __hip_atomic_load(p.coop_timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0);
+      // lane i watches granules i and i + 64 (those below 4 S)
+      unsigned long long v0 = tag, v1 = tag;
+      unsigned spins = 0;
+      while (ok) {
+        if (lane < 4 * S) v0 = __hip_atomic_load(g + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane + 64 < 4 * S)
+          v1 = __hip_atomic_load(g + lane + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__all((v0 & 0xffffffff00000000ull) == tag && (v1 & 0xffffffff00000000ull) == tag))
+          break;
+        __builtin_amdgcn_s_sleep(2);
+        ++spins;
+        if ((spins & 1023u) == 0 &&
+            __builtin_amdgcn_readfirstlane(__hip_atomic_load(p.coop_timeout, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT)) != 0)
+          ok = 0;   // another replicate's exchange already gave up: stop waiting (uniform)
+        if (spins > (1u << 22)) {
+          if (lane == 0) atomicExch(p.coop_timeout, 1);
+          ok = 0;
+        }
+      }
+      // slice-ordered sums through LDS (sred[5 ..]), value j on lane j
+      if (lane < 4 * S) sred[5 + lane] = __uint_as_float((unsigned)v0);
+      if (lane + 64 < 4 * S) sred[5 + lane + 64] = __uint_as_float((unsigned)v1);
+      __builtin_amdgcn_wave_barrier();
+      if (lane < 4) {
+        float t = 0.f;
+        if (ok) {
+          for (int s2 = 0; s2 < S; ++s2) t += sred[5 + 4 * s2 + lane];
+        }
+        sred[lane] = t;
+        if (lane == 0) sred[4] = ok ? 1.f : 0.f;
+      }
+    }
+  }
+  if (!wait) return true;
+  __syncthreads();
+  a = sred[0];
+  b = sred[1];
+  c = sred[2];
+  d = sred[3];
+  const bool good = sred[4] != 0.f;
   __syncthreads();
   return good;
 }

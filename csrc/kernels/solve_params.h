@@ -27,7 +27,7 @@ struct SolveParams {
   // per-epoch partial sums are exchanged through global memory (deterministic order) as
   // {tag = coop_gen, value} granules (coop_sum2 in solve_core.h), never zeroed between
   // eager launches: coop_gen strictly increases per workspace.
-  unsigned long long* coop_slots;   // [R][coop_epochs][S][2] granules
+  unsigned long long* coop_slots;   // [R][coop_epochs][S][2] granules ([4]: solve_pipe.h)
   unsigned coop_gen;
   int coop_epochs;
   int* coop_timeout;        // set to 1 if a spin gave up (residency violated)

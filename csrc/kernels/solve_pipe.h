@@ -75,6 +75,16 @@ __host__ __device__ constexpr int pipe_lds_floats(int K, int T) {
              : 64 * (16 * pipe_mb(K) + 1);
 }
 
+// Instantiations whose sweep 0 also forms the initial objective (kFold0 in the kernel): a
+// second inlined copy of the sweep with the two running sums live across it.  Only
+// those that keep 4 (K <= 32) / 2 waves per SIMD with no more scratch than without it
+// (hipcc -Rpass-analysis=kernel-resource-usage, ROCm 7.2; table in docs/ARCHITECTURE.md
+// "Fixed costs per launch"): T * KS <= 28 iterate registers up to K = 32 -- but not the
+// two-tile kernels of K >= 28, which sit at 128 VGPRs already -- and <= 48 above.
+__host__ __device__ constexpr bool pipe_fold0(int K, int T) {
+  return K <= 32 ? (T * pipe_ks(K) <= 28 && !(K >= 28 && T == 2)) : T * pipe_ks(K) <= 48;
+}
+
 #define CNMF_PIPE_N(i, s) sN[((i) * KS + (s)) * (64 * kPipeWaves) + threadIdx.x]
 
 // (Gram x) of one tile: d[b][r] = component 16 b + 4 r + g of the lane's column
@@ -87,6 +97,36 @@ __device__ __forceinline__ void pipe_chain(const float (&a)[MB][KS], const float
   for (int s = 0; s < KS; ++s)
 #pragma unroll
     for (int b = 0; b < MB; ++b) d[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[b][s], x[s], d[b], 0, 0, 0);
+}
+
+// One MU sweep over the T tiles, software pipelined: chain(i + 1) in flight while tile i
+// updates.  Obj: also accumulate the block objective's terms of the x the sweep starts
+// from (x^T Gram x into qd, numer . x into ln), from the same chain, in the objective
+// pass's (i, s) order.
+template <int K, int T, bool Obj>
+__device__ __forceinline__ void pipe_sweep(const float (&a)[pipe_mb(K)][pipe_ks(K)],
+                                           float (&xr)[T][pipe_ks(K)], const float* sN,
+                                           float eps, float& qd, float& ln) {
+  constexpr int KS = pipe_ks(K);
+  constexpr int MB = pipe_mb(K);
+  f32x4p acc[2][MB];
+  pipe_chain<KS, MB>(a, xr[0], acc[0]);
+#pragma unroll
+  for (int i = 0; i < T; ++i) {
+    if (i + 1 < T) pipe_chain<KS, MB>(a, xr[i + 1], acc[(i + 1) & 1]);
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const float den = acc[i & 1][s >> 2][s & 3];
+      const float xv = xr[i][s];
+      const float nv = CNMF_PIPE_N(i, s);
+      if constexpr (Obj) {
+        qd = fmaf(xv, den, qd);
+        ln = fmaf(xv, nv, ln);
+      }
+      const float rt = nv * __builtin_amdgcn_rcpf(den);
+      xr[i][s] = (den < eps) ? 0.f : xv * rt;
+    }
+  }
 }
 
 // Launch-completion bookkeeping of the device-side generation (SolveParams.coop_gen_dev):
@@ -120,7 +160,8 @@ void solve_pipe_kernel(SolveParams p, int pl_n) {
   constexpr int KS = pipe_ks(K);
   constexpr int MB = pipe_mb(K);
   constexpr int KP = 16 * MB;          // Gram rows covered by the output blocks
-  __shared__ float sred[3 + 2 * kCoopMaxSlices];
+  constexpr bool kFold0 = pipe_fold0(K, T);
+  __shared__ float sred[5 + 4 * kCoopMaxSlices];   // block_sum2 / coop_sum4_tag_s scratch
   // numerators of this lane's columns; also the partial-Gram scratch of the epilogue
   __shared__ float sN[pipe_lds_floats(K, T)];
   // phase stamps are compiled in only for the probe build (CNMF_PIPE_STAMPS_BUILD=1 at
@@ -388,19 +429,37 @@ void solve_pipe_kernel(SolveParams p, int pl_n) {
   int epoch = 0, it = 0;
   float f_prev = 0.f;
   bool have_prev = false;
-  // <numer, x> and sum_j x_j^T Gram x_j of the CURRENT x from the last objective pass
+  // <numer, x> and sum_j x_j^T Gram x_j of the CURRENT x, summed over the workgroup and
+  // the slices by the last objective check's exchange: a solve that stops at a check
+  // has its lin / quad outputs in hand and its epilogue exchanges nothing
   float lin_p = 0.f, quad_p = 0.f;
   bool lq_valid = false;
   // The objective of the initial x is only ever the reference of the first convergence
   // test: this slice's part of it is kept and exchanged together with the first real
   // check -- one cooperative exchange (a wait on the slowest slice) fewer per solve
-  // (tools/pipe_stamp_probe.py: the checks were ~30 % of a launch).  (Folding its terms
-  // into sweep 0 instead saved the chain pass too, but the second unrolled sweep body
-  // pushed K = 20 past 128 VGPRs into scratch.)
+  // (tools/pipe_stamp_probe.py: the checks were ~30 % of a launch).  Where kFold0 holds,
+  // its terms come out of sweep 0, which runs the same chain on the same x: a copy of
+  // the sweep ahead of the loop (pipe_sweep<K, T, true>), no chain pass of its own.  (One
+  // body with a wave-uniform flag per tile splits the pipelined schedule into basic
+  // blocks and went to scratch in almost every instantiation.)
   const bool defer0 = p.max_iter > 0;
   float f0_part = 0.f;
   bool f0_pending = false;
 
+  if (kFold0 && defer0) {
+    float qd = 0.f, ln = 0.f;
+    pipe_sweep<K, T, true>(a, xr, sN, eps, qd, ln);
+    // (stamps: sweep 0 stays in the loop phase; only the reduction counts as a check)
+    const unsigned long long tf0 = stp ? __builtin_amdgcn_s_memtime() : 0ull;
+    block_sum2(qd, ln, sred);
+    f0_part = qd - 2.f * ln;
+    f0_pending = true;
+    it = 1;
+    if (stp) {
+      st_chk += __builtin_amdgcn_s_memtime() - tf0;
+      ++n_chk;
+    }
+  }
   while (true) {
     if (it % every == 0) {
       const unsigned long long tc0 = stp ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -418,57 +477,41 @@ void solve_pipe_kernel(SolveParams p, int pl_n) {
           ln = fmaf(xv, CNMF_PIPE_N(i, s), ln);
         }
       }
-      lin_p = ln;
-      quad_p = qd;
-      lq_valid = true;
       float q = qd, l = ln;
       block_sum2(q, l, sred);
       float f = q - 2.f * l;
-      if (it == 0 && defer0) {            // kept for the first real check
+      if (!kFold0 && it == 0 && defer0) {   // kept for the first real check
         f0_part = f;
         f0_pending = true;
         if (stp) {
           st_chk += __builtin_amdgcn_s_memtime() - tc0;
           ++n_chk;
         }
-        goto sweep;
-      }
-      float f0 = f0_part;
-      if (stp && rt_x == 0) rt_x = __builtin_amdgcn_s_memrealtime();   // first arrival
-      if (coop) {
-        if (!coop_sum2_tag_s(p, gen, rep, epoch++, f, f0, sred, nsg, slc)) break;
-      }
-      if (f0_pending) {       // the initial objective, summed over the slices like f
-        f_prev = f0;
+      } else {
+        float f0 = f0_part;
+        if (stp && rt_x == 0) rt_x = __builtin_amdgcn_s_memrealtime();   // first arrival
+        if (coop) {
+          if (!coop_sum4_tag_s(p, gen, rep, epoch++, f, f0, l, q, sred, nsg, slc, true)) break;
+        }
+        lin_p = l;
+        quad_p = q;
+        lq_valid = true;
+        if (f0_pending) {       // the initial objective, summed over the slices like f
+          f_prev = f0;
+          have_prev = true;
+          f0_pending = false;
+        }
+        if (stp) {
+          st_chk += __builtin_amdgcn_s_memtime() - tc0;
+          ++n_chk;
+        }
+        if (have_prev && fabsf(f_prev - f) <= p.tol * fabsf(f_prev)) break;
+        f_prev = f;
         have_prev = true;
-        f0_pending = false;
       }
-      if (stp) {
-        st_chk += __builtin_amdgcn_s_memtime() - tc0;
-        ++n_chk;
-      }
-      if (have_prev && fabsf(f_prev - f) <= p.tol * fabsf(f_prev)) break;
-      f_prev = f;
-      have_prev = true;
     }
-  sweep:
     if (it >= p.max_iter) break;
-    // one MU sweep, software pipelined: chain(i + 1) in flight while tile i updates
-    {
-    f32x4p acc[2][MB];
-    pipe_chain<KS, MB>(a, xr[0], acc[0]);
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-      if (i + 1 < T) pipe_chain<KS, MB>(a, xr[i + 1], acc[(i + 1) & 1]);
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const float den = acc[i & 1][s >> 2][s & 3];
-        const float xv = xr[i][s];
-        const float rt = CNMF_PIPE_N(i, s) * __builtin_amdgcn_rcpf(den);
-        xr[i][s] = (den < eps) ? 0.f : xv * rt;
-      }
-    }
-    }
+    pipe_sweep<K, T, false>(a, xr, sN, eps, f0_part, f0_part);   // (sums unused without Obj)
     ++it;
     lq_valid = false;
   }
@@ -518,6 +561,7 @@ void solve_pipe_kernel(SolveParams p, int pl_n) {
   }
 
   if (p.lin_out || p.quad_out) {
+    // stopped at a check: that check's exchange already summed them over the slices
     float lin = lin_p, quad = quad_p;
     if (!lq_valid) {   // stopped by max_iter: one more product for the final x
       lin = 0.f;
@@ -533,9 +577,12 @@ void solve_pipe_kernel(SolveParams p, int pl_n) {
           quad = fmaf(xr[i][s], acc[i & 1][s >> 2][s & 3], quad);
         }
       }
+      block_sum2(lin, quad, sred);
+      // only slice 0 writes the outputs: the other slices publish and go on
+      float z0 = 0.f, z1 = 0.f;
+      if (coop)
+        (void)coop_sum4_tag_s(p, gen, rep, epoch++, lin, quad, z0, z1, sred, nsg, slc, slc == 0);
     }
-    block_sum2(lin, quad, sred);
-    if (coop) (void)coop_sum2_tag_s(p, gen, rep, epoch++, lin, quad, sred, nsg, slc);
     if (threadIdx.x == 0 && (!coop || slc == 0)) {
       if (p.lin_out) p.lin_out[rep] = lin;
       if (p.quad_out) p.quad_out[rep] = quad;

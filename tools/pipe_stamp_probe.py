@@ -3,7 +3,8 @@ s_memtime stamps (diagnostic only: ops.STAMPS_ON gives each launch a stamp buffe
 that nothing else reads).  Runs one bench-shaped factorisation (graphs off, so every pass
 is an eager, stamped launch) and prints, per K and side (slice count), the mean cycles per
 workgroup in: prologue (operand loads, slab / partial-Gram sums), the sweep loop minus
-the objective checks, the checks (objective chain + block reduce + cooperative exchange),
+the objective checks, the checks (objective chain + block reduce + cooperative exchange;
+of the initial objective, which sweep 0 forms, only the block reduce),
 and the epilogue (stores, planes, partial Gram), plus the launch span (first start to
 last end) against the mean workgroup time -- the load-imbalance tail.
 
