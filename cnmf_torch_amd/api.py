@@ -43,7 +43,7 @@ from .models.consensus import (cluster_medians, kmeans, l2_normalize_rows, local
                                pairwise_distances, silhouette)
 from .models.hvg import (compute_tpm, exact_mean_var, get_highvar_genes,
                          get_highvar_genes_sparse, get_mean_var)
-from .models.nmf import NMFBatchSolver, NMFOptions, SparseTilesX
+from .models.nmf import NMFBatchSolver, NMFOptions, SparseCSRX, SparseTilesX, beta_value
 from . import ops
 from .models.ols import efficient_ols_all_cols
 from .models.pp import scale as pp_scale
@@ -854,7 +854,9 @@ class cNMF:
         ``x_storage``: "dense" (default; the resident fp32 matrix and its bf16 planes) or
         "tiles" (the matrix held once as tiles of its non-zeros, models.nmf.SparseTilesX:
         no dense copy on host or device; online Frobenius MU / HALS with random init
-        only).  None: $CNMF_X_STORAGE, else "dense".
+        only) or "csr" (the matrix held once as the CSR the sparse KL kernels read,
+        models.nmf.SparseCSRX: no dense copy on host or device; kullback-leibler MU with
+        random init on the GPU, K <= 128).  None: $CNMF_X_STORAGE, else "dense".
 
         Jobs with the same K are solved together in batches of ``replicate_batch``
         replicates (default: all of them that fit the device memory budget).
@@ -895,12 +897,14 @@ class cNMF:
         if not jobs:
             return
         x_storage = x_storage or os.environ.get("CNMF_X_STORAGE") or "dense"
-        if x_storage not in ("dense", "tiles"):
-            raise ValueError(f"x_storage {x_storage!r}: 'dense' or 'tiles'")
-        if x_storage == "tiles" and (row_range is not None or row_segments is not None
+        if x_storage not in ("dense", "tiles", "csr"):
+            raise ValueError(f"x_storage {x_storage!r}: 'dense', 'tiles' or 'csr'")
+        if x_storage != "dense" and (row_range is not None or row_segments is not None
                                      or (comm is not None and comm.world_size > 1)):
             raise ValueError("SparseTilesX (x_storage='tiles'): the cell-sharded multi-GPU "
-                             "route is not supported on tile storage")
+                             "route is not supported on tile storage" if x_storage == "tiles"
+                             else "SparseCSRX (x_storage='csr'): the cell-sharded multi-GPU "
+                             "route is not supported on csr storage")
         if row_range is not None and row_segments is None:
             row_segments = [tuple(int(v) for v in row_range)]
             contiguous = True
@@ -913,7 +917,25 @@ class cNMF:
                 torch.set_num_threads(max(1, int(kwargs["n_jobs"])))
             row_map = schedule = None
             Xd = None
-            if x_storage == "tiles":
+            if x_storage == "csr":
+                # checked before the matrix is read and before any replicate file is written
+                k_max = int(run_params["n_components"].to_numpy()[list(jobs)].max())
+                bad = [f"{k}={v!r}" for k, v, ok in (
+                    ("beta_loss", kwargs.get("beta_loss", "frobenius"),
+                     beta_value(kwargs.get("beta_loss", "frobenius")) == 1.0),
+                    ("device", str(dev), dev.type == "cuda"),
+                    ("K", k_max, k_max <= 128)) if not ok]
+                if bad:
+                    raise ValueError("SparseCSRX (x_storage='csr') supports kullback-leibler "
+                                     "MU at K <= 128 on the GPU; got " + ", ".join(bad))
+                # the file's matrix straight into the CSR holder: no resident mirror, no
+                # _dense32
+                norm_counts = read_h5ad(self.paths["normalized_counts"])
+                Xd = SparseCSRX.from_scipy(norm_counts.X, device=dev)
+                norm_counts.X = None
+                Xh = None
+                cell_idx = np.arange(norm_counts.shape[0])
+            elif x_storage == "tiles":
                 # the file's matrix (scipy CSR, or dense on disk) straight into the tile
                 # holder, row block by row block: no resident mirror, no _dense32
                 norm_counts = read_h5ad(self.paths["normalized_counts"])

@@ -63,11 +63,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--replicate-batch", type=int, default=None,
                    help="[factorize] Replicates solved together per launch (default: auto)")
     p.add_argument("--device", type=str, default=None, help="[factorize/consensus] torch device override")
-    p.add_argument("--x-storage", type=str, default=None, choices=["dense", "tiles"],
-                   help="[factorize] how the normalised counts are held: dense (default) or "
+    p.add_argument("--x-storage", type=str, default=None, choices=["dense", "tiles", "csr"],
+                   help="[factorize] how the normalised counts are held: dense (default), "
                         "tiles (64 x 64 tiles of the non-zeros, no dense copy on host or "
                         "device; online Frobenius mu / hals with random init, one GPU per "
-                        "matrix). Default: $CNMF_X_STORAGE, else dense")
+                        "matrix) or csr (the sparse KL kernels' CSR, no dense copy; "
+                        "kullback-leibler mu with random init, K <= 128, one GPU per matrix). "
+                        "Default: $CNMF_X_STORAGE, else dense")
     p.add_argument("--dp", action="store_true", default=False,
                    help="[factorize] cell-sharded data parallelism under torchrun: every rank "
                         "holds a shard of the cells, all ranks solve every replicate with the "

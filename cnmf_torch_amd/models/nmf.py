@@ -59,6 +59,7 @@ from .nmf_base import (  # noqa: F401
     NMFOptions,
     NMFResult,
     PlanesOnlyX,
+    SparseCSRX,
     SparseTilesX,
     _FUSED_MAX_SLABS,
     _LAYOUT_REPLAY,
@@ -118,6 +119,23 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
 
     def __init__(self, X: torch.Tensor, opts: NMFOptions, comm=None, row_offset: int = 0,
                  profile: bool = False, schedule=None, row_map=None):
+        if isinstance(X, SparseCSRX):
+            # csr storage: the KL kernels' CSR is the only copy of X.  Checked ahead of the
+            # options' own validation, so that the message names the holder
+            if (comm is not None and comm.is_distributed) or row_map is not None:
+                raise ValueError("SparseCSRX: the cell-sharded multi-GPU route (comm / "
+                                 "row_map) is not supported on csr storage")
+            native = X.device.type == "cuda" and ops.native_available()
+            bad = [f"{k}={v!r}" for k, v, ok in (
+                ("beta_loss", opts.beta_loss, beta_value(opts.beta_loss) == 1.0),
+                ("algo", opts.algo, opts.algo == "mu"),
+                ("init", opts.init, opts.init == "random"),
+                ("dtype", opts.dtype, opts.dtype == torch.float32),
+                ("device", str(X.device), native)) if not ok]
+            if bad:
+                raise ValueError("SparseCSRX supports KL MU (online or batch) with random init "
+                                 "in float32 on the GPU kernels (it is the only copy of X); "
+                                 "got " + ", ".join(bad))
         opts.validate()
         # optional explicit online schedule: list of steps, each a list of (row_start,
         # row_end) blocks solved independently before one W update (used to emulate the
@@ -125,8 +143,14 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
         self.schedule = schedule
         self.opts = opts
         self.comm = comm or LocalComm()
-        self._virtual = isinstance(X, (PlanesOnlyX, SparseTilesX))
-        if self._virtual:
+        self._virtual = isinstance(X, (PlanesOnlyX, SparseTilesX, SparseCSRX))
+        self._csr_src = X if isinstance(X, SparseCSRX) else None
+        if self._csr_src is not None:
+            # the same NaN-valued stand-in for X as below: shape, device and dtype only
+            self._holder = "SparseCSRX"
+            src = X
+            X = torch.full((1, 1), float("nan"), device=src.device).expand(*src.shape)
+        elif self._virtual:
             # planes (or tiles) only: X stands in as a NaN-valued (N, G) view of one element -- shape,
             # device and dtype for the bookkeeping; any read of its values would surface as
             # NaN errors, and every code path that reads X raises before it
@@ -167,7 +191,8 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
         self._ws_reserve = 0        # bytes of per-batch workspaces still to allocate (run)
         if self._virtual:
             local_sq = src.x_sq
-            self._xp = src if isinstance(src, SparseTilesX) else src.planes
+            self._xp = src if isinstance(src, SparseTilesX) else \
+                None if self._csr_src is not None else src.planes
             self._mean_x = self.comm.allreduce_scalar(src.sum) / max(
                 self.comm.allreduce_scalar(float(src.shape[0] * src.shape[1])), 1.0)
         elif self.X.device.type == "cuda" and self.X.dtype == torch.float32 and self.X.numel():
@@ -200,6 +225,9 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
             raise ValueError(f"{R} seeds but {ks.size} ranks")
         if R and ks.min() < 1:
             raise ValueError("every K must be >= 1")
+        if self._csr_src is not None and R and native_rank(int(ks.max())) > 128:
+            raise ValueError("SparseCSRX supports K <= 128 (the sparse KL kernels' ranks); "
+                             f"got K={int(ks.max())}")
         kmax = kernel_max_rank(self.beta, o.algo)
         uncovered = (self.X.device.type == "cuda" and not ops.eager_active() and R
                      and kmax is not None and int(ks.max()) > kmax)
@@ -560,6 +588,8 @@ class NMFBatchSolver(_GraphMixin, _StreamMixin, _DPMixin, _BetaMixin):
             quad = self.comm.allreduce_(quad.contiguous())
             return torch.sqrt(torch.clamp(self.x_sq - 2 * lin.cpu() + quad.cpu(), min=0.0))
         K = int(K)
+        if self._csr_src is not None:       # csr storage: the CSR loss kernel
+            return self._loss_dev(HT, W, K).cpu()
         R = W.shape[0] // K
         W3 = W.view(R, K, G)
         tot = ops.beta_loss(X, HT.view(R, K, N), W3, self.beta, self.opts.eps)

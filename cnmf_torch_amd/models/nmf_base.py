@@ -749,6 +749,109 @@ class SparseTilesX:
 
 
 
+# csr storage indexes its entries with int32 (the sparse KL kernels' rowptr / col): the
+# entry count must stay below this
+CSR_MAX_NNZ = 2 ** 31 - 1
+
+
+class SparseCSRX:
+    """A non-negative cells x genes matrix held on the device ONCE, as the CSR the sparse KL
+    kernels read (ops.KLCSR: int32 rowptr / col, fp32 val; sparse_kl*.hip) -- 8 bytes per
+    non-zero plus the row pointers, against 4 bytes per ENTRY of the dense fp32 matrix the
+    KL route otherwise derives that CSR from.  The spectra side's transposed tiles are built
+    from it on the device (ops.kl_csr_tiles_from_csr, csr_transpose.hip).  Neither the host
+    nor the device ever holds the dense matrix.  ``NMFBatchSolver`` takes it in place of X
+    for KL MU (online or batch) with random init in float32 on the GPU, K <= 128, one
+    process; every other use raises.
+
+    The arrays are checked here, on the host, before any kernel can read them: a bad
+    pointer or index would become a read outside the arrays in the kernels."""
+
+    def __init__(self, rowptr, col, val, shape, device="cpu"):
+        """From canonical host CSR arrays (numpy; see :meth:`from_scipy`)."""
+        N, G = int(shape[0]), int(shape[1])
+        rowptr, col, val = self._validate(rowptr, col, val, N, G)
+        self.shape, self.dtype = (N, G), torch.float32
+        self.device = torch.device(device)
+        nnz = self.nnz = int(col.size)
+        self.sum = float(val.sum(dtype=np.float64))
+        self.x_sq = float(np.square(val, dtype=np.float64).sum())
+        self.rowptr_host = rowptr
+
+        def up(a, dtype):       # >= 1 element: the kernels' clamped loads read entry 0
+            a = np.ascontiguousarray(a, dtype=dtype) if nnz else np.zeros(1, dtype=dtype)
+            return torch.from_numpy(a).to(self.device)
+
+        self.csr = ops.KLCSR(torch.from_numpy(rowptr).to(self.device), up(col, np.int32),
+                             up(val, np.float32), N, G)
+
+    @staticmethod
+    def _validate(rowptr, col, val, N: int, G: int, limit: bool = True):
+        """(rowptr int32, col, val) once the structure holds; ValueError otherwise."""
+        rowptr, col, val = np.asarray(rowptr), np.asarray(col), np.asarray(val)
+        nnz = int(col.size)
+        if limit and nnz >= CSR_MAX_NNZ:
+            raise ValueError(f"SparseCSRX: {nnz} non-zeros do not fit the int32 entry index "
+                             f"(limit {CSR_MAX_NNZ})")
+        if val.size != nnz or rowptr.ndim != 1 or rowptr.size != N + 1:
+            raise ValueError(f"SparseCSRX: rowptr needs {N + 1} entries and col / val one "
+                             "length")
+        rp = rowptr.astype(np.int64)
+        if int(rp[0]) != 0 or int(rp[-1]) != nnz or bool((np.diff(rp) < 0).any()):
+            raise ValueError("SparseCSRX: rowptr must start at 0, end at nnz and be monotone")
+        if nnz and (int(col.min()) < 0 or int(col.max()) >= G):
+            raise ValueError(f"SparseCSRX: column index outside 0 <= col < {G}")
+        if nnz and not bool((np.isfinite(val) & (val >= 0)).all()):
+            raise ValueError("SparseCSRX: negative or non-finite value (KL needs finite "
+                             "X >= 0)")
+        return rp.astype(np.int32), col, val
+
+    @classmethod
+    def from_scipy(cls, m, device="cpu", rows: int = 1 << 16) -> "SparseCSRX":
+        """From a scipy sparse (or dense numpy) cells x genes matrix as stored in the file:
+        a dense matrix is converted in row blocks of ``rows`` cells; duplicates are summed,
+        explicit zeros dropped and indices sorted.  The input is checked as it comes, before
+        anything is done with it."""
+        import scipy.sparse as sp
+
+        N, G = m.shape
+        if sp.issparse(m):
+            m = m.tocsr()
+            cls._validate(m.indptr, m.indices, m.data, N, G, limit=False)
+            m = sp.csr_matrix((m.data.astype(np.float32), m.indices.copy(), m.indptr.copy()),
+                              shape=(N, G))
+        else:
+            parts = [sp.csr_matrix(np.asarray(m[a:a + rows], dtype=np.float32))
+                     for a in range(0, N, rows)]
+            m = sp.vstack(parts, format="csr") if parts else sp.csr_matrix((N, G),
+                                                                           dtype=np.float32)
+            cls._validate(m.indptr, m.indices, m.data, N, G, limit=False)
+        m.sum_duplicates()
+        m.eliminate_zeros()
+        m.sort_indices()
+        return cls(m.indptr, m.indices, m.data, (N, G), device)
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes held: col and val (one element at least), the row pointers."""
+        return 8 * max(self.nnz, 1) + 4 * (self.shape[0] + 1)
+
+    def row_sum(self, a: int, b: int) -> float:
+        """sum(X[a:b]) in float64."""
+        lo, hi = int(self.rowptr_host[a]), int(self.rowptr_host[b])
+        return float(self.csr.val[lo:hi].sum(dtype=torch.float64)) if hi > lo else 0.0
+
+    def to_dense(self) -> torch.Tensor:
+        """The float32 matrix the CSR stands for (tests)."""
+        N, G = self.shape
+        rp = self.csr.rowptr.to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(N, device=rp.device), torch.diff(rp))
+        X = torch.zeros((N, G), dtype=torch.float32, device=rp.device)
+        X[rows, self.csr.col[:self.nnz].to(torch.int64)] = self.csr.val[:self.nnz]
+        return X
+
+
+
 def kernel_max_rank(beta: float, algo: str) -> int | None:
     """Largest K the native kernels factorise (None: no limit).  Frobenius MU: any K --
     register-tiled kernels up to 128 (padded, native_rank), the rank-general solve beyond

@@ -67,6 +67,12 @@ class _BetaMixin:
         64 < K <= 128; ``CNMF_KL_SPARSE=1`` forces it, ``=0`` disables it); else None
         (dense split-precision kernels, beta_any.hip above K = 64).  The density is read once
         per solver (one host sync), the route decided once per rank tier."""
+        if self._csr_src is not None:
+            # csr storage: the holder's CSR is the only copy of X, whatever its density and
+            # CNMF_KL_SPARSE (K <= 128 is checked by run)
+            if "_kl_csrT" not in self.__dict__:
+                self._kl_csrT = {}
+            return self._csr_src.csr
         K = max(getattr(self, "_beta_K", 0), self.opts.n_components)
         if K > 128:                              # the CSR kernels stop at K = 128
             return None
@@ -129,7 +135,11 @@ class _BetaMixin:
         K = self._beta_K or self.opts.n_components
         key = (a, b, ops.kl_tile_rows(K))
         if key not in self._kl_csrT:
-            self._kl_csrT[key] = ops.kl_csr_tiles(self.X[a:b], K)
+            if self._csr_src is not None:   # csr storage: transposed on the device
+                self._kl_csrT[key] = ops.kl_csr_tiles_from_csr(
+                    ops.kl_csr_rows(self._csr_src.csr, a, b), K)
+            else:
+                self._kl_csrT[key] = ops.kl_csr_tiles(self.X[a:b], K)
         return self._kl_csrT[key]
 
     def _beta_w_partials(self, xc, xtc, H3c, W3, active, panels=None, rows=None):
@@ -152,11 +162,18 @@ class _BetaMixin:
         return ops.beta_w_partials(xc, xtc, H3c, W3, self.beta, self.opts.eps, active=active,
                                    panels=panels)
 
-    def _chunk_xsum(self, xc: torch.Tensor) -> float:
+    def _chunk_xsum(self, xc: torch.Tensor, rows=None) -> float:
         """sum(X) of a row block in float64 (the KL objective's linear term), cached per
-        block: X never changes, so this host sync happens once per block per solver."""
-        key = (xc.data_ptr(), tuple(xc.shape))
+        block: X never changes, so this host sync happens once per block per solver.  On csr
+        storage the block is named by its row range ``rows`` (the view that stands in for X
+        has one address for every block) and summed from the CSR values."""
         cache = self.__dict__.setdefault("_xsum_cache", {})
+        if self._csr_src is not None:
+            key = ("rows", int(rows[0]), int(rows[1]))
+            if key not in cache:
+                cache[key] = self._csr_src.row_sum(*key[1:])
+            return cache[key]
+        key = (xc.data_ptr(), tuple(xc.shape))
         if key not in cache:
             cache[key] = float(xc.sum(dtype=torch.float64))
         return cache[key]
@@ -206,7 +223,8 @@ class _BetaMixin:
         per = max(1, int(o.inner_check_every)) if cmode == 1 else 1
         group = 1 if cmode == 1 else block
         hstate = torch.zeros((W3.shape[0], 2), dtype=torch.float64, device=xc.device)
-        xsum = self._chunk_xsum(xc) if (cuda and self.beta == 1.0 and cmode == 1) else None
+        xsum = self._chunk_xsum(xc, rows) if (cuda and self.beta == 1.0 and cmode == 1) \
+            else None
         max_it = int(o.online_chunk_max_iter)
         pending = None
         it = 0

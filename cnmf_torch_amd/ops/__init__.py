@@ -1402,6 +1402,44 @@ def kl_csr_tiles(Xc: torch.Tensor, K: int) -> list:
     return [(t0, kl_csr(Xc[t0:min(c, t0 + tl)].t())) for t0 in range(0, c, tl)]
 
 
+def kl_csr_tiles_from_csr(csr_rows: KLCSR, K: int) -> list:
+    """:func:`kl_csr_tiles` of a row chunk given as its CSR rows (:func:`kl_csr_rows` of a
+    device CSR) instead of a dense slice: the same [(t0, CSR of the tile's transpose)],
+    entry for entry, built by csr_transpose.hip (count / scan / scatter / place; the result
+    does not depend on the order of its integer atomics).  The tiles of the chunk share one
+    col / val allocation and carry absolute row pointers, as :func:`kl_csr_rows` does.  One
+    host read (the chunk's entry range)."""
+    _require_native()
+    rp, col, val = csr_rows.rowptr, csr_rows.col, csr_rows.val
+    c, G = int(csr_rows.n_rows), int(csr_rows.n_cols)
+    dev = rp.device
+    tl = kl_tile_rows(K)
+    if (rp.dtype != torch.int32 or col.dtype != torch.int32 or val.dtype != torch.float32
+            or rp.numel() != c + 1 or not (rp.is_contiguous() and col.is_contiguous()
+                                           and val.is_contiguous())
+            or dev.type != "cuda" or col.device != dev or val.device != dev):
+        raise ValueError("kl_csr_tiles_from_csr: contiguous int32 rowptr (n_rows + 1) / col "
+                         "and float32 val on one GPU required")
+    if tl > int(_hip.csr_transpose_max_tile()):
+        raise ValueError(f"kl_csr_tiles_from_csr: tile of {tl} rows")
+    lo, hi = rp[[0, c]].tolist() if c else (0, 0)
+    if not (0 <= lo <= hi <= min(col.numel(), val.numel())):
+        raise ValueError(f"kl_csr_tiles_from_csr: entries [{lo}, {hi}) outside col / val")
+    T = -(-c // tl)
+    nnz = hi - lo
+    # >= 1 element: the sparse KL kernels' clamped loads read entry 0 of an empty matrix
+    colT = torch.zeros(max(nnz, 1), dtype=torch.int32, device=dev)
+    valT = torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev)
+    rpT = torch.empty((T, G + 1), dtype=torch.int32, device=dev)
+    cnt = torch.empty(max(T * G, 1), dtype=torch.int32, device=dev)
+    tmp = torch.empty((max(nnz, 1), 2), dtype=torch.int32, device=dev)
+    _hip.csr_transpose_tiles(rp.data_ptr(), col.data_ptr(), val.data_ptr(), c, G, tl, lo, hi,
+                             cnt.data_ptr(), tmp.data_ptr(), rpT.data_ptr(), colT.data_ptr(),
+                             valT.data_ptr(), _stream_ptr(rp))
+    return [(t * tl, KLCSR(rpT[t], colT, valT, G, min(c, (t + 1) * tl) - t * tl))
+            for t in range(T)]
+
+
 def kl_st(F3: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """(R, L, K4) transpose of F3 (R, K, L), rows zero-padded to K4 = 4 ceil(K / 4) (the
     sparse KL kernels gather one float4-aligned row per non-zero)."""

@@ -410,3 +410,27 @@ def count_unit_check(X: torch.Tensor, mn: torch.Tensor) -> torch.Tensor:
         off &= X != 0
         bad |= (off.any(0) & ok_col).to(torch.int32) << (d - 1)
     return bad
+
+
+def csr_transpose_tiles(rowptr, col, val, a: int, b: int, G: int, tl: int) -> list:
+    """Transposed tile CSRs of rows [a, b) of a CSR matrix (``rowptr`` with absolute
+    offsets, ``col``, ``val``; torch tensors or numpy arrays) -- the contract of
+    csr_transpose.hip: [(t0, rowptr_t (G + 1, int32, from 0), col_t (int32), val_t
+    (float32))] over tiles of ``tl`` rows, tile t the CSR of X[a + t0 : a + t1]^T with G
+    rows, the cell's index inside the tile as column, ascending within a gene."""
+    rp = torch.as_tensor(rowptr).to(torch.int64).cpu()
+    col = torch.as_tensor(col).cpu()
+    val = torch.as_tensor(val).cpu()
+    out = []
+    for t0 in range(0, b - a, tl):
+        t1 = min(b - a, t0 + tl)
+        lo, hi = int(rp[a + t0]), int(rp[a + t1])
+        g = col[lo:hi].to(torch.int64)
+        cell = torch.repeat_interleave(torch.arange(t1 - t0), torch.diff(rp[a + t0:a + t1 + 1]))
+        order = torch.argsort(g * (t1 - t0) + cell)       # (gene, cell) keys are unique
+        rpt = torch.zeros(G + 1, dtype=torch.int64)
+        rpt[1:] = torch.bincount(g, minlength=G).cumsum(0)
+        out.append((t0, rpt.to(torch.int32), cell[order].to(torch.int32),
+                    val[lo:hi].to(torch.float32)[order]))
+    return out
+

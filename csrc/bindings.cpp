@@ -283,6 +283,18 @@ PYBIND11_MODULE(_hip, m) {
                 "sk_run");
         });
 
+  m.def("csr_transpose_max_tile", []() { return cnmf_csr_transpose_max_tile(); });
+  m.def("csr_transpose_tiles",
+        [](uintptr_t rowptr, uintptr_t col, uintptr_t val, int c, int G, int tl, int lo, int hi,
+           uintptr_t cnt, uintptr_t tmp, uintptr_t rowptrT, uintptr_t colT, uintptr_t valT,
+           uintptr_t stream) {
+          check(cnmf_csr_transpose_tiles(P<const int>(rowptr), P<const int>(col),
+                                         P<const float>(val), c, G, tl, lo, hi, P<int>(cnt),
+                                         P<void>(tmp), P<int>(rowptrT), P<int>(colT),
+                                         P<float>(valT), reinterpret_cast<hipStream_t>(stream)),
+                "csr_transpose_tiles");
+        });
+
   m.def("pairdist", [](uintptr_t A, long long lda, uintptr_t B, long long ldb, uintptr_t na,
                        uintptr_t nb, int n, int mm, int kdim, uintptr_t D, long long ldd, int same,
                        int squared, uintptr_t stream) {

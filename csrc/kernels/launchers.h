@@ -117,6 +117,12 @@ hipError_t cnmf_sk_run(int side, const int* rowptr, const int* col, const float*
                        int* act, int* iters, const int* active, double* loss, double xsum,
                        hipStream_t stream);
 
+// csr_transpose.hip: transposed tile CSRs of a row chunk of a device CSR matrix
+int cnmf_csr_transpose_max_tile();
+hipError_t cnmf_csr_transpose_tiles(const int* rowptr, const int* col, const float* val, int c,
+                                    int G, int tl, int lo, int hi, int* cnt, void* tmp,
+                                    int* rowptrT, int* colT, float* valT, hipStream_t stream);
+
 hipError_t cnmf_pairdist(const double* A, long long lda, const double* B, long long ldb,
                          const double* na, const double* nb, int n, int m, int kdim, double* D,
                          long long ldd, int same, int squared, hipStream_t stream);
