@@ -700,7 +700,7 @@ def conv_update(lin: torch.Tensor, quad: torch.Tensor, x_sq: float, state: dict,
     replicate stops after its own max_pass-th pass (replicates of a streaming batch sit
     at different passes).  ``gate`` (int32 device scalar): set to 1 while any replicate
     is active, else 0 (gemm_planes ``gate``).  ``host_flags`` (GPU): (flags, counter) --
-    pinned int32 (2, >= n) and an int32 device scalar; the launch also stores the active
+    pinned int32 (2, n) and an int32 device scalar; the launch also stores the active
     flags into ``flags[counter % 2]`` through the host mapping and advances the counter,
     so the host reads a pass's flags after its event without a copy launch (the caller
     mirrors the counter: _PassPipeline)."""
@@ -747,7 +747,11 @@ def stream_swap(grp: dict, ring: dict, store: dict, state: tuple, gate: torch.Te
     (int32 device scalars), ids (qc,), W (qc K, G), HT (qc K, N), sf (3, qc) float64, si
     (5, qc) int32, parts (qc, S, K, K), wpl (3, qc K, Gp); ``store``: offs (R,) int64, W,
     HT (or None), sf (3, R), si (5, R), done (int32 scalar); ``state``: the batch's (sf,
-    si) row views at the group's first position (3 / 5 rows, any row stride)."""
+    si) row views at the group's first position (3 / 5 rows, any row stride).  In every
+    state table the float64 ``sf`` rows are err_init, err_prev, err and the int32 ``si``
+    rows are active, converged, n_pass, h_iters, w_iters (the arena's layout,
+    models/nmf_batch.py); a column is a position (batch), a ring slot or a replicate id
+    (store).  ``grp["active"]`` is the group's slice of ``si`` row 0."""
     n, K = int(grp["n"]), int(grp["K"])
     if n <= 0:
         return

@@ -105,8 +105,18 @@ def philox_fill(out: torch.Tensor, seeds, scales, stream: int, mode: int = 0,
         out[r].copy_((m * scales[r]).to(out.dtype))
 
 
+def _sqrt_f64(x: torch.Tensor) -> torch.Tensor:
+    """Correctly rounded square root, as the device's: torch's vectorised CPU sqrt is
+    1 ulp off for some float64 inputs, numpy's is the IEEE one."""
+    if x.device.type != "cpu":
+        return torch.sqrt(x)
+    with np.errstate(invalid="ignore"):
+        return torch.from_numpy(np.sqrt(x.contiguous().numpy()))
+
+
 def conv_update(lin, quad, x_sq, state, n, pass_idx, tol, final, init=False, max_pass=0):
-    e = torch.sqrt(torch.clamp(x_sq - 2.0 * lin[:n].double() + quad[:n].double(), min=0.0))
+    # (clamp keeps a NaN radicand NaN: non-finite statistics propagate, as in conv.hip)
+    e = _sqrt_f64(torch.clamp(x_sq - 2.0 * lin[:n].double() + quad[:n].double(), min=0.0))
     e = e.to(state["err"].device)
     if init:
         for k in ("err_init", "err_prev", "err"):

@@ -3,6 +3,10 @@
 // Frobenius loss from the W-solve epilogue's sufficient statistics:
 //   err = sqrt(max(||X||^2 - 2 <B, W> + <A, W W^T>, 0))  (sklearn square_root=True)
 // and the nmf-torch / sklearn stopping rule (prev - cur) / init < tol.
+// Non-finite statistics propagate, as in ops.reference.conv_update: only a radicand below
+// 0 (-inf included) is clamped, so a NaN lin / quad gives err = NaN (+inf stays +inf), the
+// floor on err_init keeps a NaN, and a comparison with NaN is false -- such a replicate is
+// never marked converged and stops only at final_pass / max_pass.
 // Keeping this on the device lets the host enqueue pass p+1 before it has read pass p's
 // result: the solves skip replicates whose `active` flag dropped, so the host only polls
 // the flags one pass behind instead of draining the GPU at every pass boundary.
@@ -24,7 +28,8 @@ __global__ void __launch_bounds__(256) conv_update_kernel(
   const int slot = hflags ? (*hcnt & 1) : 0;   // read before thread 0 advances it below
   int any = 0;
   for (int r = threadIdx.x; r < n; r += blockDim.x) {
-    const double e = sqrt(fmax(x_sq - 2.0 * (double)lin[r] + (double)quad[r], 0.0));
+    const double rad = x_sq - 2.0 * (double)lin[r] + (double)quad[r];
+    const double e = sqrt(rad < 0.0 ? 0.0 : rad);   // (not fmax: that would turn NaN into 0)
     if (init) {  // error of the initial factors
       err_init[r] = e;
       err_prev[r] = e;
@@ -39,7 +44,7 @@ __global__ void __launch_bounds__(256) conv_update_kernel(
     err[r] = e;
     const int np = pass >= 0 ? pass : n_pass[r] + 1;   // pass < 0: count on device (graphs)
     n_pass[r] = np;
-    const double denom = err_init[r] > 1e-300 ? err_init[r] : 1e-300;
+    const double denom = err_init[r] < 1e-300 ? 1e-300 : err_init[r];
     if ((err_prev[r] - e) / denom < tol) {
       active[r] = 0;
       converged[r] = 1;
