@@ -70,13 +70,13 @@ class NMFOptions:
     # r4c_kl_*; CSR vs dense rep/s): 8 % 564 / 381, 15 % 403 / 365, 25 % 290 / 348,
     # 35 % 228 / 338 -- equal near 19 %; at the headline's 47 % the dense kernels win
     kl_sparse_density: float = 0.18
-    # the same threshold for 32 < K <= 64 (sparse_kl_wide.hip).  Measured
+    # the same threshold for 32 < K <= 64 (sparse_kl.hip, 4 component slices).  Measured
     # (profiles/p2_kl_wide_ab.txt; CSR vs dense rep/s): K = 48: 8 % 98 / 64, 15 % 60 / 62,
     # 25 % 39 / 62; K = 64: 8 % 69 / 57, 15 % 44 / 55, 25 % 29 / 55 -- the time per
     # replicate is linear in the density on the CSR side and flat on the dense one, equal
     # near 14 % (K = 48) and 10.7 % (K = 64); one threshold below both
     kl_sparse_density_wide: float = 0.10
-    # the same threshold for 64 < K <= 128 (sparse_kl_xwide.hip); above K = 64 the dense
+    # the same threshold for 64 < K <= 128 (sparse_kl.hip, 8 slices); above K = 64 the dense
     # route is the rank-general one (beta_any.hip).  Measured (profiles/p3_kl_xwide_ab.txt;
     # CSR vs dense rep/s): K = 80: 8 % 52.6 / 12.2, 15 % 33.9 / 11.9, 25 % 22.7 / 11.9,
     # 35 % 17.4 / 11.8; K = 128: 8 % 34.3 / 9.8, 15 % 21.4 / 9.6, 25 % 13.9 / 9.5,

@@ -61,7 +61,7 @@ class _BetaMixin:
 
     def _kl_sparse(self):
         """CSR of X (ops.KLCSR) when the KL MU statistics run on the sparse kernels
-        (sparse_kl.hip, sparse_kl_wide.hip above K = 32, sparse_kl_xwide.hip above K = 64):
+        (sparse_kl.hip: one slice of components per lane up to K = 32, 4 to 64, 8 to 128):
         KL on the native GPU path at K <= 128 with X at most ``kl_sparse_density`` non-zero
         (``kl_sparse_density_wide`` for 32 < K <= 64, ``kl_sparse_density_xwide`` for
         64 < K <= 128; ``CNMF_KL_SPARSE=1`` forces it, ``=0`` disables it); else None

@@ -1367,10 +1367,9 @@ def beta_w_partials(X: torch.Tensor, XT: torch.Tensor | None, HT3: torch.Tensor,
 
 # ------------------------------------------------------------- sparse KL (CSR X)
 class KLCSR(NamedTuple):
-    """CSR of a non-negative matrix for the sparse KL kernels (sparse_kl.hip, K <= 32;
-    sparse_kl_wide.hip, 33 <= K <= 64; sparse_kl_xwide.hip, 65 <= K <= 128): row i owns
-    entries [rowptr[i], rowptr[i+1]) of col / val; a row range is a rowptr slice over the
-    same col / val (:func:`kl_csr_rows`)."""
+    """CSR of a non-negative matrix for the sparse KL kernels (sparse_kl.hip, K <= 128): row
+    i owns entries [rowptr[i], rowptr[i+1]) of col / val; a row range is a rowptr slice over
+    the same col / val (:func:`kl_csr_rows`)."""
     rowptr: torch.Tensor    # int32 (n_rows + 1,), absolute offsets
     col: torch.Tensor       # int32
     val: torch.Tensor       # float32
@@ -1481,8 +1480,8 @@ def kl_sparse_h_block(csr: KLCSR, HT3: torch.Tensor, W3: torch.Tensor, eps: floa
                       xsum: float | None = None) -> None:
     """:func:`beta_h_block` at beta = 1 over the CSR rows ``csr`` (cells x genes) of X:
     ``nsteps`` fused KL MU steps of HT3 (R, K, c) in place against W3 (R, K, G), the same
-    on-device stopping rule (side 0 of sparse_kl.hip, sparse_kl_wide.hip above K = 32,
-    sparse_kl_xwide.hip above K = 64; K <= 128).  ``st``: :func:`kl_st` of W3."""
+    on-device stopping rule (side 0 of sparse_kl.hip; K <= 128).  ``st``: :func:`kl_st` of
+    W3."""
     R, K, N = HT3.shape
     if tol is not None and act is None:
         raise ValueError("the stopping rule needs an act array")
@@ -1538,8 +1537,8 @@ def kl_sparse_w_num(tiles: list, HT3: torch.Tensor, W3: torch.Tensor, eps: float
                     st: torch.Tensor | None = None) -> torch.Tensor:
     """KL spectra numerators num = HT Q over a row chunk given as :func:`kl_csr_tiles`
     (cells tiled so that each tile's usages fit in LDS), as (tiles, R, K, G) partials -- the
-    :func:`beta_w_partials` layout (side 1 of sparse_kl.hip, sparse_kl_wide.hip above K = 32,
-    sparse_kl_xwide.hip above K = 64; K <= 128).  ``st``: :func:`kl_st` of HT3."""
+    :func:`beta_w_partials` layout (side 1 of sparse_kl.hip; K <= 128).  ``st``:
+    :func:`kl_st` of HT3."""
     R, K, c = HT3.shape
     G = W3.shape[2]
     _require_native()

@@ -2,7 +2,7 @@
 // data matrix, models.nmf_base.SparseCSRX): for the chunk's c rows (cells) split into tiles
 // of tl rows, the CSR of every tile's transpose -- G rows (genes), columns = the cell's
 // index inside the tile, ascending within a gene -- which is what the spectra side of the
-// sparse KL kernels (sparse_kl*.hip, side 1) streams.  All tiles of the chunk share one
+// sparse KL kernel (sparse_kl.hip, side 1) streams.  All tiles of the chunk share one
 // col / val allocation (a tile's entries are contiguous in the source, so tile t starts at
 // rowptr[t tl] - rowptr[0]) and carry absolute row pointers, (T, G + 1).
 //

@@ -102,8 +102,8 @@ hipError_t cnmf_bp_run(int side, int mode, const float* X, long long ldx,
                        int* act, int* iters, const int* active, double* loss, double xsum,
                        int xh, const float* uvec, const float* fscale, hipStream_t stream);
 
-// sparse_kl.hip: KL MU statistics over a CSR matrix, K <= 128 (33..64: sparse_kl_wide.hip,
-// 65..128: sparse_kl_xwide.hip)
+// sparse_kl.hip: KL MU statistics over a CSR matrix, K <= 128 (one kernel template, its
+// instance chosen by the padded rank)
 int cnmf_sk_k4(int K);
 int cnmf_sk_lds(int Ls, int K);
 int cnmf_sk_cols_per_wg(int Lf, int R, int Ls, int K);

@@ -258,7 +258,7 @@ def _csr_kl():
 @pytest.mark.parametrize("eps", BETA_EPSES)
 @pytest.mark.parametrize("K,G", SPARSE_DEGENERATE_CASES)
 def test_sparse_kl_degenerate(K, G, eps):
-    """sparse_kl.hip (K <= 32), sparse_kl_wide.hip (33-64) and sparse_kl_xwide.hip (65-128),
+    """sparse_kl.hip with 1 (K <= 32), 4 (33-64) and 8 (65-128) component slices,
     W^T staged in LDS and gathered from L2: usage blocks with the rule, loss and spectra
     numerators with a dead spectrum, dead usages, an empty gene and cells without usage
     (eps + P = eps exactly)."""
@@ -294,8 +294,8 @@ def test_solver_from_nndsvd_gpu_matches_cpu(route, K):
 
 @pytest.mark.parametrize("K", [6, 40])
 def test_sparse_kl_solver_from_nndsvd_gpu_matches_cpu(K):
-    """The same on the CSR kernels (CNMF_KL_SPARSE=1; sparse_kl.hip at K = 6,
-    sparse_kl_wide.hip at 40) on the ~15 %-dense matrix."""
+    """The same on the CSR kernels (CNMF_KL_SPARSE=1; sparse_kl.hip, one slice at
+    K = 6, four at 40) on the ~15 %-dense matrix."""
     from cnmf_torch_amd.models.nmf import NMFBatchSolver, NMFOptions
 
     X = sparse_counts()

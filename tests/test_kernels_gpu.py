@@ -1040,11 +1040,18 @@ def test_online_kl_matches_fp32_torch_path(numer, monkeypatch):
     ops.refresh_env()
 
 
-@pytest.mark.parametrize("K,G", [(3, 333), (10, 333), (17, 333), (32, 1200)])
+# every one-slice instance of the dispatch, K4 / 4 = 1 .. 8: K = 3, 5, 10, 13, 17, 24, 28, 32
+@pytest.mark.parametrize("K,G", [(3, 333), (10, 333), (17, 333), (32, 1200),
+                                 (5, 333), (13, 333), (24, 333), (28, 333)])
 def test_sparse_kl_kernels_match_fp64(K, G):
-    """sparse_kl.hip (CSR X, fp32 gathers) vs the float64 dense reference: a 3-step usage
-    block with the block-objective rule, the spectra numerators and the loss (W^T staged
-    in LDS; K = 32, G = 1200 exceeds the LDS budget and gathers from L2)."""
+    """sparse_kl.hip at K <= 32 (CSR X, fp32 gathers) vs the float64 dense reference: three
+    3-step usage blocks with the block-objective rule, the spectra numerators and the loss
+    (W^T staged in LDS; K = 32, G = 1200 exceeds the LDS budget and gathers from L2).  A
+    wrong quad count in the dispatch would drop components or read past the padded row, so
+    the cases take every instance.  In the reference every replicate of every case ends with
+    iters [6, 6, 6] and act [0, 0, 0]: the block objective changes by 0.65-0.97 after block 1
+    (0.79-0.97 at K = 5, 13, 24, 28) and by 0.0019-0.0066 after block 2 (0.0051-0.0066 at
+    those four) against tol 0.05, so no stop decision is near its threshold."""
     g = torch.Generator().manual_seed(K)
     R, N = 3, 901
     X = torch.rand((N, G), generator=g, dtype=torch.float64)
@@ -1085,6 +1092,7 @@ def test_sparse_kl_kernels_match_fp64(K, G):
                               tol=0.05, iters=it_g, hstate=hs_g, loss_entry=blk == 0)
         reference.beta_h_block(X[a:b], h2, W, 1.0, eps, 3, 0.01, 0.0, act=act_r, tol=0.05,
                                iters=it_r, hstate=hs_r, loss_entry=blk == 0)
+    assert it_r.tolist() == [6, 6, 6] and act_r.tolist() == [0, 0, 0]
     torch.testing.assert_close(h1.cpu().double(), h2, rtol=1e-4, atol=1e-6)
     assert act_g.cpu().tolist() == act_r.tolist()
     assert it_g.cpu().tolist() == it_r.tolist()

@@ -219,7 +219,7 @@ def _sparse_blocks(K, G, pens, act0):
 @pytest.mark.parametrize("pens", BETA_SETS)
 @pytest.mark.parametrize("K,G", SPARSE_CASES)
 def test_sparse_kl_h_block_penalised(K, G, pens):
-    """sparse_kl.hip (K <= 32) and sparse_kl_wide.hip, W^T staged in LDS and gathered:
+    """sparse_kl.hip with one component slice (K <= 32) and four, W^T staged in LDS and gathered:
     three 3-step blocks with the rule (tol 0.05) against the float64 dense reference.  In
     float64 the block objective changes by 0.90-0.99 after block 1 and 0.002-0.007 after
     block 2 at these inputs under every penalty set."""
@@ -322,8 +322,8 @@ def test_kl_solver_with_alpha_gpu_matches_cpu(mode, alpha):
 
 @pytest.mark.parametrize("K,alpha", [(6, 600.0), (40, 100.0)])
 def test_sparse_kl_solver_with_alpha_gpu_matches_cpu(K, alpha):
-    """Online KL on the CSR kernels (CNMF_KL_SPARSE=1; sparse_kl.hip at K = 6,
-    sparse_kl_wide.hip at 40) on the ~15 %-dense matrix of
+    """Online KL on the CSR kernels (CNMF_KL_SPARSE=1; sparse_kl.hip, one slice at
+    K = 6, four at 40) on the ~15 %-dense matrix of
     test_online_kl_wide_sparse_path_matches_dense.  Four passes of <= 20 inner steps, no
     outer stop (tol -1), so the CPU side stays quick and a rising err under the penalty
     cannot end the two runs at different passes.  err moves by 27 % ... 30 % at K = 6,

@@ -103,8 +103,8 @@ def _same_result(a, b):
 @pytest.mark.parametrize("K,mode", [(5, "online"), (40, "online"), (72, "online"),
                                     (5, "batch")])
 def test_solver_on_the_holder_equals_dense_storage_bitwise(monkeypatch, K, mode):
-    """The two routes hand identical arrays to identical kernels (one rank per CSR kernel
-    file: sparse_kl.hip, sparse_kl_wide.hip, sparse_kl_xwide.hip)."""
+    """The two routes hand identical arrays to identical kernels (one rank per slice count
+    of sparse_kl.hip: 1, 4 and 8 component slices)."""
     monkeypatch.setenv("CNMF_KL_SPARSE", "1")
     X = _counts(700, 150, 0.10, 5)
     if mode == "online":

@@ -1,4 +1,4 @@
-"""Sparse KL (CSR) kernels at 33 <= K <= 64 (sparse_kl_wide.hip): numerics vs the float64
+"""Sparse KL (CSR) kernels at 33 <= K <= 64 (sparse_kl.hip, 4 slices): numerics vs the float64
 reference, the replicate gate, the solver on the CSR route against the dense route, and the
 automatic routing above K = 32."""
 import os

@@ -1,4 +1,4 @@
-"""Sparse KL (CSR) kernels at 65 <= K <= 128 (sparse_kl_xwide.hip): numerics vs the float64
+"""Sparse KL (CSR) kernels at 65 <= K <= 128 (sparse_kl.hip, 8 slices): numerics vs the float64
 reference, the penalties, the replicate gate, the solver on the CSR route against the dense
 route (beta_any.hip), and the automatic routing above K = 64."""
 import functools
