@@ -47,7 +47,7 @@ from .models.nmf import NMFBatchSolver, NMFOptions, SparseCSRX, SparseTilesX, be
 from . import ops
 from .models.ols import efficient_ols_all_cols
 from .models.pp import scale as pp_scale
-from .models.refit import col_block, fit_H_online, fit_spectra_online, gene_blocks
+from .models.refit import col_block, fit_H_online, fit_spectra_online, gene_blocks, refit_beta
 from .ops import sparse as sops
 from .parallel.ledger import worker_filter
 from .utils.anndata_lite import AnnData
@@ -1213,24 +1213,43 @@ class cNMF:
             self._yaml_cache = cache
         return dict(cache[1])
 
-    def refit_usage(self, X, spectra, usage=None, device=None):
-        """Refit usages with spectra fixed (cnmf.py:923-976): online MU, h_tol 0.05."""
+    def _refit_loss(self, loss):
+        """The loss a refit minimises: None / "frobenius" (the default, the reference's
+        refit whatever the run's loss), "kullback-leibler", or "match" = the ``beta_loss`` of
+        the run parameters (beta 2 -> Frobenius, beta 1 -> KL; any other beta raises: its
+        refit needs every entry of the product)."""
+        if loss is None:
+            return "frobenius"
+        if loss == "match":
+            run_loss = self._refit_kwargs().get("beta_loss", "frobenius")
+            b = beta_value(run_loss)
+            if b not in (1.0, 2.0):
+                raise ValueError(f"refit loss 'match': the run's beta_loss={run_loss!r} has no "
+                                 "refit; supported are 'frobenius' (2) and 'kullback-leibler' (1)")
+            return "kullback-leibler" if b == 1.0 else "frobenius"
+        return "kullback-leibler" if refit_beta(loss) == 1.0 else "frobenius"
+
+    def refit_usage(self, X, spectra, usage=None, device=None, loss=None):
+        """Refit usages with spectra fixed (cnmf.py:923-976): online MU, h_tol 0.05.
+        ``loss``: see :meth:`_refit_loss`."""
         kw = self._refit_kwargs()
         dev = _device(bool(kw.get("use_gpu", False)), device)
         return fit_H_online(X, spectra, H_init=usage, chunk_size=kw["online_chunk_size"],
                             chunk_max_iter=kw["online_chunk_max_iter"], h_tol=0.05,
                             l1_reg_H=kw.get("l1_ratio_H", 0.0), l2_reg_H=0.0, epsilon=1e-16,
-                            device=dev)
+                            device=dev, beta_loss=self._refit_loss(loss))
 
-    def refit_spectra(self, X, usage, device=None, comm=None):
+    def refit_spectra(self, X, usage, device=None, comm=None, loss=None):
         """Refit spectra with usages fixed (cnmf.py:979-994).  With a multi-rank ``comm``
         the genes are sharded over the ranks in whole refit chunks (tensor/gene-axis
-        parallelism) and the K x G blocks are all-gathered."""
+        parallelism) and the K x G blocks are all-gathered.
+        ``loss``: see :meth:`_refit_loss`."""
         kw = self._refit_kwargs()
         dev = _device(bool(kw.get("use_gpu", False)), device)
         u = usage.values if isinstance(usage, pd.DataFrame) else np.asarray(usage)
         args = dict(chunk_size=kw["online_chunk_size"], chunk_max_iter=kw["online_chunk_max_iter"],
-                    h_tol=0.05, l1_reg=kw.get("l1_ratio_H", 0.0), device=dev)
+                    h_tol=0.05, l1_reg=kw.get("l1_ratio_H", 0.0), device=dev,
+                    beta_loss=self._refit_loss(loss))
         if comm is None or comm.world_size == 1:
             return fit_spectra_online(X, u, **args)
         g0, g1 = gene_blocks(X.shape[1], kw["online_chunk_size"], comm.world_size)[comm.rank]
@@ -1243,22 +1262,27 @@ class cNMF:
                   show_clustering=True, build_ref=True, skip_density_and_return_after_stats=False,
                   close_clustergram_fig=False, refit_usage=True, normalize_tpm_spectra=False,
                   norm_counts=None, kmeans_backend="auto", device=None, comm=None,
-                  wait_figures=True):
-        """Consensus spectra/usages for one K (cnmf.py:997-1256).  With a multi-rank
+                  wait_figures=True, refit_loss="frobenius"):
+        """Consensus spectra/usages for one K (cnmf.py:997-1256).  ``refit_loss``: the loss
+        of the three refits -- "frobenius" (default: the reference's refit, whatever the
+        run's loss) or "match" (the run's ``beta_loss``: a KL run is refit under KL).  With a multi-rank
         ``comm`` the two all-gene passes -- the TPM spectra refit and the OLS gene scores
         over G_all -- are sharded over the ranks by gene blocks (the clustering is
         replicated); rank 0 writes the artifacts.  ``wait_figures=False`` (closed figures
         only): return before the clustergram PNG is written; it finishes while the caller
         goes on (utils.plotting.flush_figures, which the CLI calls before exiting)."""
+        self._refit_loss(refit_loss)     # an unsupported loss raises before any work
         with self.timer(f"consensus_k{k}"):
             return self._consensus(k, density_threshold, local_neighborhood_size, show_clustering,
                                    build_ref, skip_density_and_return_after_stats,
                                    close_clustergram_fig, refit_usage, normalize_tpm_spectra,
-                                   norm_counts, kmeans_backend, device, comm, wait_figures)
+                                   norm_counts, kmeans_backend, device, comm, wait_figures,
+                                   refit_loss)
 
     def _consensus(self, k, density_threshold, local_neighborhood_size, show_clustering,
                    build_ref, skip_stats, close_fig, refit_usage, normalize_tpm_spectra,
-                   norm_counts, kmeans_backend, device, comm=None, wait_figures=True):
+                   norm_counts, kmeans_backend, device, comm=None, wait_figures=True,
+                   refit_loss="frobenius"):
         tp = comm is not None and comm.world_size > 1
         writer = not tp or comm.rank == 0
         # a closed clustergram is drawn by a child process that imports matplotlib while
@@ -1332,7 +1356,7 @@ class cNMF:
         # so two of them must not share the GPU: serialised across the k-selection
         # threads (everything else of a K -- npz read, k-means, medians -- overlaps)
         with _COOP_LOCK:
-            rf_usages = self.refit_usage(ncX, median_spectra, device=dev)
+            rf_usages = self.refit_usage(ncX, median_spectra, device=dev, loss=refit_loss)
         rf_usages = pd.DataFrame(rf_usages, index=norm_counts.obs.index, columns=median_spectra.index)
 
         if skip_stats:
@@ -1362,7 +1386,7 @@ class cNMF:
         dT = _device_csr_cached(tpm, dev)
         tpmX = dT if dT is not None else tpm.X
         spectra_tpm = self.refit_spectra(tpmX, norm_usages.astype(tpm.X.dtype), device=dev,
-                                         comm=comm if tp else None)
+                                         comm=comm if tp else None, loss=refit_loss)
         spectra_tpm = pd.DataFrame(spectra_tpm, index=new_cols, columns=tpm.var.index)
         if normalize_tpm_spectra:
             spectra_tpm = spectra_tpm.div(spectra_tpm.sum(axis=1), axis=0) * 1e6
@@ -1403,7 +1427,8 @@ class cNMF:
                 norm_X, norm_dtype = norm_tpm.X, norm_tpm.X.dtype
             spectra_tpm_rf = spectra_tpm.loc[:, hvgs]
             spectra_tpm_rf = spectra_tpm_rf.div(tpm_stats.loc[hvgs, "__std"], axis=1)
-            rf = self.refit_usage(norm_X, spectra_tpm_rf.astype(norm_dtype), device=dev)
+            rf = self.refit_usage(norm_X, spectra_tpm_rf.astype(norm_dtype), device=dev,
+                                  loss=refit_loss)
             rf_usages = pd.DataFrame(rf, index=norm_counts.obs.index, columns=spectra_tpm_rf.index)
         del dT, tpmX
 

@@ -7,8 +7,8 @@ commented out at cnmf.py:1430) and gives ``--total-workers`` its documented mean
 shards the ledger over ranks automatically, one rank per GPU.
 
 Additions: ``--algo``/``--mode`` (prepare), ``--replicate-batch``, ``--device``,
-``--save-usages``, ``--x-storage`` (factorize), ``--kmeans-backend``, ``--no-build-reference``
-(consensus), ``--skip-missing-files`` (combine).
+``--save-usages``, ``--x-storage`` (factorize), ``--kmeans-backend``, ``--no-build-reference``,
+``--refit-loss`` (consensus), ``--skip-missing-files`` (combine).
 """
 from __future__ import annotations
 
@@ -97,6 +97,10 @@ def build_parser() -> argparse.ArgumentParser:
                    choices=["auto", "sklearn", "device"],
                    help="[consensus] auto (device on GPU, else sklearn), sklearn (the "
                         "reference's exact KMeans) or device (batched GPU k-means)")
+    p.add_argument("--refit-loss", type=str, default="frobenius", choices=["frobenius", "match"],
+                   help="[consensus] Loss of the usage / spectra refits: frobenius (the "
+                        "reference's refit whatever the run's loss) or match (the run's "
+                        "--beta-loss: a kullback-leibler run is refit under KL)")
     return p
 
 
@@ -163,13 +167,15 @@ def main(argv=None) -> int:
 
             distributed_consensus(obj, ks, args.local_density_threshold,
                                   args.local_neighborhood_size, args.show_clustering,
-                                  args.build_reference, kmeans_backend=args.kmeans_backend)
+                                  args.build_reference, kmeans_backend=args.kmeans_backend,
+                                  refit_loss=args.refit_loss)
         else:
             for k in ks:
                 obj.consensus(k, args.local_density_threshold, args.local_neighborhood_size,
                               args.show_clustering, args.build_reference,
                               close_clustergram_fig=True, kmeans_backend=args.kmeans_backend,
-                              device=args.device, wait_figures=False)
+                              device=args.device, wait_figures=False,
+                              refit_loss=args.refit_loss)
     elif args.command == "k_selection_plot":
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             from .parallel.runner import distributed_k_selection

@@ -15,6 +15,13 @@ denominator < eps (cnmf.py:348-381).  Differences by design (SURVEY.md App. B #4
 
 ``fit_spectra_online`` is ``refit_spectra`` (cnmf.py:979-994, ``refit_usage(X.T,
 usage.T).T``) without materialising ``X.T`` densely: its numerator is ``U^T X``.
+
+``beta_loss="kullback-leibler"`` (or 1) refits under KL instead -- the reference parses
+``beta_loss`` in ``refit_usage`` and then ignores it; the original cNMF refits under the run's
+loss.  Same chunks, seeded init and chunk rule; the MU step is the KL usage step over the
+non-zeros of X held as CSR (ops.kl_sparse_refit: sparse_kl.hip's chunk-batched mode, one
+launch per step for all chunks), the spectra side the same on the device transpose of that
+CSR (ops.csr_transpose).  The default stays Frobenius.
 """
 from __future__ import annotations
 
@@ -166,17 +173,112 @@ def gene_blocks(G: int, chunk: int, world: int) -> list[tuple[int, int]]:
     return out
 
 
+REFIT_LOSSES = {"frobenius": 2.0, "kullback-leibler": 1.0}
+
+
+def refit_beta(beta_loss) -> float:
+    """2.0 (Frobenius) or 1.0 (KL) for the losses a refit supports, by name or by beta."""
+    if isinstance(beta_loss, str):
+        b = REFIT_LOSSES.get(beta_loss)
+    elif isinstance(beta_loss, (int, float, np.integer, np.floating)) and \
+            not isinstance(beta_loss, bool) and float(beta_loss) in (1.0, 2.0):
+        b = float(beta_loss)
+    else:
+        b = None
+    if b is None:
+        raise ValueError(f"refit: beta_loss={beta_loss!r} is not supported; the refits minimise "
+                         "'frobenius' (2) or 'kullback-leibler' (1)")
+    return b
+
+
+def kl_csr_of(X, device) -> "ops.KLCSR":
+    """X (n x G) as the float32 CSR of the sparse KL kernels on ``device``, never densified
+    there: a dense device tensor through ops.kl_csr, a DeviceCSR (also a lazy scaled /
+    column-mapped view: materialised once through ops.sparse.transform), host dense or
+    scipy input uploaded as CSR."""
+    dev = torch.device(device)
+    if isinstance(X, ops.KLCSR):
+        return X
+    if isinstance(X, sops.DeviceCSR):
+        n, G = X.shape
+        if X.nnz >= 2 ** 31:
+            raise ValueError(f"KL refit: {X.nnz} stored entries do not fit int32 offsets")
+        val = sops.transform(X, out_dtype=torch.float32) if X.xf else X.data.to(torch.float32)
+        col = X.indices
+        rowptr = X.indptr
+        cm = X.xf.get("col_map")
+        if cm is not None:                  # dropped columns leave the matrix
+            col = torch.as_tensor(cm, dtype=torch.int32).to(X.device)[col.long()]
+            keep = col >= 0
+            cnt = torch.bincount(X.row_ids()[keep], minlength=n)
+            rowptr = torch.zeros(n + 1, dtype=torch.int64, device=X.device)
+            rowptr[1:] = cnt.cumsum(0)
+            col, val = col[keep], val[keep]
+        pad = 1 if val.numel() == 0 else 0  # the kernels' clamped loads read entry 0
+        if pad:
+            col, val = torch.zeros(1, dtype=torch.int32, device=X.device), \
+                torch.zeros(1, dtype=torch.float32, device=X.device)
+        return ops.KLCSR(rowptr.to(torch.int32).to(dev).contiguous(),
+                         col.to(torch.int32).to(dev).contiguous(), val.to(dev).contiguous(),
+                         n, G)
+    if isinstance(X, torch.Tensor):
+        return ops.kl_csr(X.to(device=dev, dtype=torch.float32))
+    m = sp.csr_matrix(X, dtype=np.float32)
+    if not m.has_canonical_format:
+        m = m.copy()
+        m.sum_duplicates()
+    m.eliminate_zeros()
+    if m.nnz >= 2 ** 31:
+        raise ValueError(f"KL refit: {m.nnz} stored entries do not fit int32 offsets")
+    pad = 1 if m.nnz == 0 else 0
+    return ops.KLCSR(torch.from_numpy(m.indptr.astype(np.int32)).to(dev),
+                     torch.from_numpy(np.concatenate([m.indices.astype(np.int32),
+                                                      np.zeros(pad, np.int32)])).to(dev),
+                     torch.from_numpy(np.concatenate([m.data, np.zeros(pad, np.float32)])).to(dev),
+                     m.shape[0], m.shape[1])
+
+
+def kl_chunked_refit(csr, HT: torch.Tensor, W: torch.Tensor, chunk_size: int, chunk_max_iter: int,
+                     h_tol: float, l1: float = 0.0, l2: float = 0.0, eps: float = 1e-16,
+                     iters: torch.Tensor | None = None) -> torch.Tensor:
+    """The KL counterpart of :func:`chunked_solve`: HT (K x n) in place against W (K x G)
+    over the CSR rows of X (ops.kl_sparse_refit, sparse_kl.hip up to K = 128).  A larger
+    rank on the GPU runs the eager PyTorch ops there, logged once, as the Frobenius refit
+    does for ranks without a kernel."""
+    K = HT.shape[0]
+    if HT.device.type == "cuda" and ops.use_native(HT) and K > 128:
+        from .nmf import _warn_once
+
+        _warn_once(f"KL refit K={K}: the native gfx950 sparse KL step covers K <= 128; this "
+                   "refit runs the eager PyTorch ops on the GPU (slower)")
+        with ops.eager_ops():
+            return ops.kl_sparse_refit(csr, HT, W, chunk_size, chunk_max_iter, h_tol, l1=l1,
+                                       l2=l2, eps=eps, iters=iters)
+    return ops.kl_sparse_refit(csr, HT, W, chunk_size, chunk_max_iter, h_tol, l1=l1, l2=l2,
+                               eps=eps, iters=iters)
+
+
 def fit_H_online(X, W, H_init=None, chunk_size: int = 5000, chunk_max_iter: int = 200,
                  h_tol: float = 0.05, l1_reg_H: float = 0.0, l2_reg_H: float = 0.0,
                  epsilon: float = 1e-16, device="cpu", random_state: int = 0,
-                 return_tensor: bool = False):
-    """Refit H (n x K) >= 0 minimising ||X - H W|| with W (K x G) fixed (cnmf.py:260)."""
+                 return_tensor: bool = False, beta_loss="frobenius", iters=None):
+    """Refit H (n x K) >= 0 with W (K x G) fixed (cnmf.py:260), minimising ||X - H W||
+    (``beta_loss`` "frobenius" / 2) or D_KL(X | H W) ("kullback-leibler" / 1: the same
+    chunks, seeded init and chunk rule, KL MU steps over the non-zeros of X held as CSR;
+    ``iters``: int32 tensor that receives the per-chunk step counts)."""
+    kl = refit_beta(beta_loss) == 1.0
     dev = torch.device(device)
     dtype = torch.float32
     Wt = torch.as_tensor(np.asarray(_to_numpy_2d(W), dtype=np.float32)).to(dev)
     Xv = X.values if isinstance(X, pd.DataFrame) else X
     K = Wt.shape[0]
     n = Xv.shape[0]
+    if kl:
+        csr = kl_csr_of(Xv, dev)
+        HT = _init_HT(K, n, H_init, dev, dtype, random_state)
+        kl_chunked_refit(csr, HT, Wt.contiguous(), chunk_size, chunk_max_iter, h_tol,
+                         l1=l1_reg_H, l2=l2_reg_H, eps=epsilon, iters=iters)
+        return HT.t() if return_tensor else HT.t().cpu().numpy()
     numerT = numer_rows(Wt, Xv)
     gram = ops.small_gram(Wt, rows_are_points=False)      # W W^T (segsum.hip)
     HT = _init_HT(K, n, H_init, dev, dtype, random_state)
@@ -189,18 +291,28 @@ def fit_H_online(X, W, H_init=None, chunk_size: int = 5000, chunk_max_iter: int 
 
 def fit_spectra_online(X, usage, chunk_size: int = 5000, chunk_max_iter: int = 200,
                        h_tol: float = 0.05, l1_reg: float = 0.0, epsilon: float = 1e-16,
-                       device="cpu", random_state: int = 0, col_offset: int = 0):
+                       device="cpu", random_state: int = 0, col_offset: int = 0,
+                       beta_loss="frobenius", iters=None):
     """Refit spectra S (K x G) >= 0 minimising ||X - U S|| with usages U (n x K) fixed.
 
     Equals ``fit_H_online(X.T, U.T).T`` (cnmf.py:994): chunks run over genes.
     ``col_offset``: X holds the genes [col_offset, col_offset + G) of a larger matrix (a
     gene-sharded rank): the seeded init is taken at those genes, so shards reproduce
-    the unsharded refit when they hold whole chunks (gene_blocks)."""
+    the unsharded refit when they hold whole chunks (gene_blocks).
+    ``beta_loss`` "kullback-leibler" / 1 minimises D_KL(X | U S) instead: the KL usage
+    refit of X^T, the CSR of X transposed on the device (ops.csr_transpose)."""
+    kl = refit_beta(beta_loss) == 1.0
     dev = torch.device(device)
     Ut = torch.as_tensor(np.asarray(_to_numpy_2d(usage), dtype=np.float32)).to(dev)
     Xv = X.values if isinstance(X, pd.DataFrame) else X
     K = Ut.shape[1]
     G = Xv.shape[1]
+    if kl:
+        csrT = ops.csr_transpose(kl_csr_of(Xv, dev))        # genes x cells
+        ST = _init_HT(K, G, None, dev, torch.float32, random_state, row_offset=col_offset)
+        kl_chunked_refit(csrT, ST, Ut.t().contiguous(), chunk_size, chunk_max_iter, h_tol,
+                         l1=l1_reg, eps=epsilon, iters=iters)
+        return ST.cpu().numpy()
     numerT = numer_cols(Ut, Xv)          # (K x G) = (X^T U)^T
     gram = ops.small_gram(Ut)                             # U^T U (segsum.hip)
     ST = _init_HT(K, G, None, dev, torch.float32, random_state, row_offset=col_offset)

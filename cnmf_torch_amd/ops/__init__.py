@@ -1559,6 +1559,144 @@ def kl_sparse_w_num(tiles: list, HT3: torch.Tensor, W3: torch.Tensor, eps: float
     return num
 
 
+def _csr_range(name: str, csr: KLCSR) -> tuple[int, int]:
+    """Entry range [lo, hi) of a CSR (one host read), checked against col / val and int32."""
+    rp = csr.rowptr
+    n = int(csr.n_rows)
+    if rp.numel() != n + 1:
+        raise ValueError(f"{name}: rowptr has {rp.numel()} entries for {n} rows")
+    lo, hi = (int(v) for v in rp[[0, n]].tolist())
+    if hi - lo >= 2 ** 31 or hi >= 2 ** 31:
+        raise ValueError(f"{name}: {hi - lo} stored entries do not fit int32 offsets")
+    if not 0 <= lo <= hi <= min(csr.col.numel(), csr.val.numel()):
+        raise ValueError(f"{name}: entries [{lo}, {hi}) outside col / val")
+    return lo, hi
+
+
+def csr_transpose(csr: KLCSR) -> KLCSR:
+    """The CSR of the transpose of ``csr`` (any row count): row pointers from 0, the entries
+    of a transposed row ordered by source row -- the arrays of scipy's ``X.T.tocsr()`` with
+    sorted indices, the same from run to run.  On the GPU: the tile transposes of
+    csr_transpose.hip (tiles of 8192 rows, bitmap ranking) merged per column by a scan over
+    (column, tile) and one copy per segment; no float atomics, no sort.  int32 offsets: a
+    matrix with 2^31 or more stored entries raises."""
+    n, G = int(csr.n_rows), int(csr.n_cols)
+    lo, hi = _csr_range("csr_transpose", csr)
+    nnz = hi - lo
+    dev = csr.col.device
+    if not use_native(csr.val):
+        rp, col, val = reference.csr_transpose(csr.rowptr, csr.col, csr.val, n, G)
+        return KLCSR(rp, col, val, G, n)
+    rp = csr.rowptr.to(torch.int32).contiguous()
+    if (csr.col.dtype != torch.int32 or csr.val.dtype != torch.float32 or rp.device != dev
+            or csr.val.device != dev or not (csr.col.is_contiguous() and csr.val.is_contiguous())):
+        raise ValueError("csr_transpose: contiguous int32 col and float32 val on one GPU required")
+    # >= 1 element: the sparse KL kernels' clamped loads read entry 0 of an empty matrix
+    colG = torch.zeros(max(nnz, 1), dtype=torch.int32, device=dev)
+    valG = torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev)
+    rpG = torch.zeros(G + 1, dtype=torch.int32, device=dev)
+    if nnz == 0 or n == 0 or G == 0:
+        return KLCSR(rpG, colG, valG, G, n)
+    tl = int(_hip.csr_transpose_max_tile())
+    T = -(-n // tl)
+    colT = torch.empty(nnz, dtype=torch.int32, device=dev)
+    valT = torch.empty(nnz, dtype=torch.float32, device=dev)
+    rpT = torch.empty((T, G + 1), dtype=torch.int32, device=dev)
+    cnt = torch.empty(T * G, dtype=torch.int32, device=dev)
+    tmp = torch.empty((nnz, 2), dtype=torch.int32, device=dev)
+    tot = torch.empty(G, dtype=torch.int32, device=dev)
+    stream = _stream_ptr(rp)
+    _hip.csr_transpose_tiles(rp.data_ptr(), csr.col.data_ptr(), csr.val.data_ptr(), n, G, tl, lo,
+                             hi, cnt.data_ptr(), tmp.data_ptr(), rpT.data_ptr(), colT.data_ptr(),
+                             valT.data_ptr(), stream)
+    _hip.csr_transpose_merge(rpT.data_ptr(), colT.data_ptr(), valT.data_ptr(), T, G, tl, nnz,
+                             cnt.data_ptr(), tot.data_ptr(), rpG.data_ptr(), colG.data_ptr(),
+                             valG.data_ptr(), stream)
+    return KLCSR(rpG, colG, valG, G, n)
+
+
+def kl_refit_chunks(n: int, chunk_size: int) -> tuple[int, int, int]:
+    """(rows per chunk, full chunks, rows of the ragged tail) of a chunked refit of n rows."""
+    c = max(1, min(int(chunk_size), int(n)))
+    full = n // c
+    return c, full, n - full * c
+
+
+def kl_sparse_refit(csr: KLCSR, HT: torch.Tensor, W: torch.Tensor, chunk_size: int,
+                    max_iter: int, tol: float, l1: float = 0.0, l2: float = 0.0,
+                    eps: float = 1e-16, iters: torch.Tensor | None = None,
+                    check_every: int = 8) -> torch.Tensor:
+    """KL refit of the usages HT (K x n, in place) against fixed spectra W (K x G) over the
+    CSR rows of X (n x G): independent chunks of ``chunk_size`` rows, each up to ``max_iter``
+    KL MU steps (denominator sum_g W_kg + l1 + l2 h, ``eps`` where it is 0) until its
+    iterate change ``||h_new - h|| / (||h|| + eps) < tol``.  On the GPU (K <= 128) one launch
+    of the chunk-batched mode of sparse_kl.hip is one step of every still-active full chunk
+    (on-device rule, finished chunks return at the gate), the ragged tail a second launch;
+    the host reads "any chunk active" every ``check_every`` steps.  ``iters`` (int32, one
+    entry per chunk) receives the step counts.  CPU tensors, and any tensor inside
+    :func:`eager_ops`, run :func:`reference.kl_refit`."""
+    K, n = HT.shape
+    G = int(W.shape[1])
+    if W.shape[0] != K or csr.n_rows != n or csr.n_cols != G:
+        raise ValueError(f"kl_sparse_refit: CSR {csr.n_rows} x {csr.n_cols}, HT {tuple(HT.shape)}, "
+                         f"W {tuple(W.shape)} do not match")
+    c, full, tail = kl_refit_chunks(n, chunk_size)
+    nch = full + (1 if tail else 0)
+    if iters is not None and (iters.dtype != torch.int32 or iters.numel() < nch
+                              or iters.device != HT.device or not iters.is_contiguous()):
+        raise ValueError(f"iters: contiguous int32 with >= {nch} entries on {HT.device}")
+    if n == 0 or int(max_iter) <= 0:
+        return HT
+    if not use_native(HT):
+        reference.kl_refit(csr, HT, W, chunk_size, max_iter, tol, l1=l1, l2=l2, eps=eps,
+                           iters=iters)
+        return HT
+    _native_dtype_k("KL refit", HT.dtype, K, 128)
+    dev = HT.device
+    _bp_check("HT", HT, dev)
+    _bp_check("W", W, dev)
+    rp = csr.rowptr
+    if (rp.dtype != torch.int32 or csr.col.dtype != torch.int32 or csr.val.dtype != torch.float32
+            or not (rp.is_contiguous() and csr.col.is_contiguous() and csr.val.is_contiguous())
+            or rp.device != dev or csr.col.device != dev or csr.val.device != dev):
+        raise ValueError("kl_sparse_refit: contiguous int32 rowptr / col and float32 val on "
+                         "HT's GPU required")
+    if HT.stride(0) < n:
+        raise ValueError("kl_sparse_refit: HT rows overlap")
+    lo, hi = _csr_range("kl_sparse_refit", csr)
+    if hi > lo:
+        cmin, cmax = (int(v) for v in torch.aminmax(csr.col[lo:hi]))
+        if cmin < 0 or cmax >= G:
+            raise ValueError(f"kl_sparse_refit: column indices [{cmin}, {cmax}] outside [0, {G})")
+    st = kl_st(W.unsqueeze(0))[0]
+    den = W.sum(dim=1, dtype=torch.float32).contiguous()
+    act = torch.ones(nch, dtype=torch.int32, device=dev)
+    it = iters if iters is not None else torch.zeros(nch, dtype=torch.int32, device=dev)
+    counter = torch.zeros(nch, dtype=torch.int32, device=dev)
+    ng_f = int(_hip.sk_groups(c, full, G, K)) if full else 0
+    ng_t = int(_hip.sk_groups(tail, 1, G, K)) if tail else 0
+    part = torch.empty((full * ng_f + ng_t) * 4 + 1, dtype=torch.float64, device=dev)
+    stream = _stream_ptr(HT)
+    a = full * c
+    every = max(1, int(check_every))
+    for s in range(int(max_iter)):
+        if full:
+            _hip.sk_refit_step(rp.data_ptr(), csr.col.data_ptr(), csr.val.data_ptr(),
+                               st.data_ptr(), HT.data_ptr(), HT.stride(0), K, c, G, full,
+                               float(eps), den.data_ptr(), float(l1), float(l2), float(tol),
+                               part.data_ptr(), counter.data_ptr(), act.data_ptr(),
+                               it.data_ptr(), stream)
+        if tail:
+            _hip.sk_refit_step(rp.data_ptr() + 4 * a, csr.col.data_ptr(), csr.val.data_ptr(),
+                               st.data_ptr(), HT.data_ptr() + 4 * a, HT.stride(0), K, tail, G, 1,
+                               float(eps), den.data_ptr(), float(l1), float(l2), float(tol),
+                               part.data_ptr() + 32 * full * ng_f, counter.data_ptr() + 4 * full,
+                               act.data_ptr() + 4 * full, it.data_ptr() + 4 * full, stream)
+        if (s + 1) % every == 0 and s + 1 < int(max_iter) and not bool(act.any()):
+            break
+    return HT
+
+
 # ----------------------------------------------------------------------------- gram
 def gram(X3: torch.Tensor, out: torch.Tensor | None = None, accumulate: bool = False,
          active: torch.Tensor | None = None) -> torch.Tensor:

@@ -444,3 +444,70 @@ def csr_transpose_tiles(rowptr, col, val, a: int, b: int, G: int, tl: int) -> li
                     val[lo:hi].to(torch.float32)[order]))
     return out
 
+
+
+def csr_transpose(rowptr, col, val, n: int, G: int):
+    """Torch twin of ops.csr_transpose: (rowptr (G + 1, int32, from 0), col (int32, the
+    source row), val) of the transpose of an (n x G) CSR, the entries of a transposed row
+    ordered by source row (a stable sort by column of the row-major entries)."""
+    rp = rowptr.long()
+    lo, hi = (int(rp[0]), int(rp[n])) if n else (0, 0)
+    c = col[lo:hi].long()
+    rows = torch.repeat_interleave(torch.arange(n, device=c.device), rp[1:n + 1] - rp[:n])
+    order = torch.sort(c, stable=True).indices
+    out_rp = torch.zeros(G + 1, dtype=torch.int64, device=c.device)
+    if hi > lo:
+        out_rp[1:] = torch.bincount(c, minlength=G).cumsum(0)
+    pad = 1 if hi == lo else 0      # the kernels' clamped loads read entry 0
+    out_col = torch.zeros(hi - lo + pad, dtype=torch.int32, device=c.device)
+    out_val = torch.zeros(hi - lo + pad, dtype=val.dtype, device=c.device)
+    out_col[:hi - lo] = rows[order].to(torch.int32)
+    out_val[:hi - lo] = val[lo:hi][order]
+    return out_rp.to(torch.int32), out_col, out_val
+
+
+def kl_refit(csr, HT, W, chunk_size, max_iter, tol, l1=0.0, l2=0.0, eps=1e-16, iters=None,
+             trace=None):
+    """Reference of ops.kl_sparse_refit (sparse_kl.hip, chunk-batched usage step), in the
+    dtype of HT: for every chunk of ``chunk_size`` rows of the CSR matrix ``csr`` (rowptr,
+    col, val, n, G), up to ``max_iter`` KL MU steps of HT[:, chunk] (K x c) against the
+    fixed W (K x G) -- p = eps + h . W[:, g] on the stored entries, num = sum_g W_kg x / p,
+    denominator sum_g W_kg + l1 + l2 h (eps where it is 0) -- until the step's iterate change
+    ||h_new - h|| / (||h|| + eps) < tol.  ``iters``: per-chunk step counts are added.
+    ``trace``: a list that receives (chunk, step, change) of every step."""
+    rowptr, col, val, n, G = csr
+    K = HT.shape[0]
+    dt = HT.dtype
+    Wd = W.to(dt)
+    WT = Wd.t().contiguous()
+    den0 = Wd.sum(dim=1)
+    c = max(1, min(int(chunk_size), int(n))) if n else 1
+    rp = rowptr.long()
+    for ci, a in enumerate(range(0, n, c)):
+        b = min(n, a + c)
+        lo, hi = int(rp[a]), int(rp[b])
+        S = WT[col[lo:hi].long()]                                # (e, K)
+        x = val[lo:hi].to(dt)
+        rows = torch.repeat_interleave(torch.arange(b - a, device=HT.device),
+                                       rp[a + 1:b + 1] - rp[a:b])
+        h = HT[:, a:b].clone()
+        steps = 0
+        for _ in range(int(max_iter)):
+            p = eps + (S * h.t()[rows]).sum(dim=1)
+            q = x / p
+            num = torch.zeros((b - a, K), dtype=dt, device=HT.device)
+            num.index_add_(0, rows, q[:, None] * S)
+            dn = den0[:, None] + l1 + l2 * h
+            dn = torch.where(dn == 0, torch.full_like(dn, eps), dn)
+            hn = h * (num.t() / dn)
+            rel = float(torch.linalg.vector_norm((hn - h).double())
+                        / (torch.linalg.vector_norm(h.double()) + eps))
+            h = hn
+            steps += 1
+            if trace is not None:
+                trace.append((ci, steps, rel))
+            if rel < tol:
+                break
+        HT[:, a:b] = h
+        if iters is not None:
+            iters[ci] += steps

@@ -145,7 +145,7 @@ def gather_merged_spectra(obj, comm, collect: dict, run_params, dev) -> None:
 
 def distributed_consensus(obj, ks, density_threshold=0.5, local_neighborhood_size=0.30,
                           show_clustering=True, build_ref=True, kmeans_backend="auto",
-                          backend: str | None = None):
+                          backend: str | None = None, refit_loss: str = "frobenius"):
     """Consensus over the ranks.  With at least as many Ks as ranks: K parallelism (rank r
     runs ``consensus`` for ``ks[r::world]`` on its own GPU; every K writes its own
     artifacts, so the ranks share no files).  With fewer Ks than ranks (typically the one
@@ -157,13 +157,13 @@ def distributed_consensus(obj, ks, density_threshold=0.5, local_neighborhood_siz
         for k in ks[comm.rank::comm.world_size]:
             obj.consensus(k, density_threshold, local_neighborhood_size, show_clustering,
                           build_ref, close_clustergram_fig=True, kmeans_backend=kmeans_backend,
-                          device=dev)
+                          device=dev, refit_loss=refit_loss)
     else:
         for k in ks:
             obj.consensus(k, density_threshold, local_neighborhood_size,
                           show_clustering and comm.rank == 0, build_ref,
                           close_clustergram_fig=True, kmeans_backend=kmeans_backend, device=dev,
-                          comm=comm)
+                          comm=comm, refit_loss=refit_loss)
     comm.barrier()
     return comm
 

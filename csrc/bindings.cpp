@@ -283,6 +283,29 @@ PYBIND11_MODULE(_hip, m) {
                 "sk_run");
         });
 
+  m.def("sk_refit_step",
+        [](uintptr_t rowptr, uintptr_t col, uintptr_t val, uintptr_t ST, uintptr_t F,
+           long long ldf, int K, int c, int Ls, int R, float eps, uintptr_t den_vec, float l1,
+           float l2, float tol, uintptr_t part, uintptr_t counter, uintptr_t act,
+           uintptr_t iters, uintptr_t stream) {
+          check(cnmf_sk_refit_step(P<const int>(rowptr), P<const int>(col), P<const float>(val),
+                                   P<const float>(ST), P<float>(F), ldf, K, c, Ls, R, eps,
+                                   P<const float>(den_vec), l1, l2, tol, P<double>(part),
+                                   P<int>(counter), P<int>(act), P<int>(iters),
+                                   reinterpret_cast<hipStream_t>(stream)),
+                "sk_refit_step");
+        });
+
+  m.def("csr_transpose_merge",
+        [](uintptr_t rowptrT, uintptr_t colT, uintptr_t valT, int T, int G, int tl, int n_ent,
+           uintptr_t pre, uintptr_t tot, uintptr_t rowptrG, uintptr_t colG, uintptr_t valG,
+           uintptr_t stream) {
+          check(cnmf_csr_transpose_merge(P<const int>(rowptrT), P<const int>(colT),
+                                         P<const float>(valT), T, G, tl, n_ent, P<int>(pre),
+                                         P<int>(tot), P<int>(rowptrG), P<int>(colG),
+                                         P<float>(valG), reinterpret_cast<hipStream_t>(stream)),
+                "csr_transpose_merge");
+        });
   m.def("csr_transpose_max_tile", []() { return cnmf_csr_transpose_max_tile(); });
   m.def("csr_transpose_tiles",
         [](uintptr_t rowptr, uintptr_t col, uintptr_t val, int c, int G, int tl, int lo, int hi,

@@ -153,6 +153,67 @@ __global__ __launch_bounds__(kCtThreads) void ct_place_kernel(
   }
 }
 
+// ---- the transpose of the whole matrix: the tile transposes merged per gene.  A gene's
+// row is its tile segments one after the other (tiles ascend in cell index, a segment
+// ascends inside its tile), so the entries of a row are ordered by cell.  Three launches:
+//   prefix  one thread per gene: pre[t][g] = entries of gene g in the tiles before t, tot[g]
+//   scan    one workgroup: exclusive scan of tot over the genes -> the global row pointers
+//   merge   one wave per (tile, gene) segment: copied to rowptr[g] + pre[t][g], the cell
+//           index made global.  No atomics at all.
+__global__ __launch_bounds__(kCtThreads) void ct_gene_prefix_kernel(
+    const int* __restrict__ rowptrT, int T, int G, int* __restrict__ pre,
+    int* __restrict__ tot) {
+  const int g = blockIdx.x * kCtThreads + threadIdx.x;
+  if (g >= G) return;
+  int run = 0;
+  for (int t = 0; t < T; ++t) {
+    const int* __restrict__ rp = rowptrT + (long long)t * (G + 1) + g;
+    pre[(long long)t * G + g] = run;
+    run += max(rp[1] - rp[0], 0);
+  }
+  tot[g] = run;
+}
+
+__global__ __launch_bounds__(kCtThreads) void ct_total_scan_kernel(
+    const int* __restrict__ tot, int G, int* __restrict__ out) {
+  __shared__ int wsum[kCtWaves];
+  int carry = 0;
+  for (int g0 = 0; g0 < G; g0 += kCtThreads) {
+    const int g = g0 + threadIdx.x;
+    const int v = g < G ? tot[g] : 0;
+    int sum;
+    const int inc = ct_block_scan(v, wsum, sum);
+    if (g < G) out[g] = carry + inc - v;
+    carry += sum;
+  }
+  if (threadIdx.x == 0) out[G] = carry;
+}
+
+__global__ __launch_bounds__(kCtThreads) void ct_merge_kernel(
+    const int* __restrict__ rowptrT, int G, int tl, long long n_seg, int n_ent,
+    const int* __restrict__ pre, const int* __restrict__ rowptrG,
+    const int* __restrict__ colT, const float* __restrict__ valT, int* __restrict__ colG,
+    float* __restrict__ valG) {
+  const int lane = threadIdx.x & 63;
+  const long long step = (long long)gridDim.x * kCtWaves;
+  for (long long seg = (long long)blockIdx.x * kCtWaves + (threadIdx.x >> 6); seg < n_seg;
+       seg += step) {
+    const int t = (int)(seg / G), g = (int)(seg - (long long)t * G);
+    const int* __restrict__ rp = rowptrT + (long long)t * (G + 1) + g;
+    const int s0 = max(rp[0], 0);
+    const int s1 = min(rp[1], n_ent);
+    const int d0 = rowptrG[g] + pre[seg];
+    const int cell0 = t * tl;
+    for (int j = lane; j < s1 - s0; j += 64) {
+      const int d = d0 + j;
+      if ((unsigned)d < (unsigned)n_ent) {
+        colG[d] = colT[s0 + j] + cell0;
+        valG[d] = valT[s0 + j];
+      }
+    }
+  }
+}
+
 }  // namespace cnmf
 
 extern "C" int cnmf_csr_transpose_max_tile() { return cnmf::kCtMaxTile; }
@@ -185,6 +246,32 @@ extern "C" hipError_t cnmf_csr_transpose_tiles(const int* rowptr, const int* col
     const long long n_seg = T * G;
     hipLaunchKernelGGL(ct_place_kernel, dim3((unsigned)(n_seg < kCtMaxGrid ? n_seg : kCtMaxGrid)),
                        blk, 0, stream, rowptrT, G, (int)n_seg, hi - lo, tmp2, colT, valT);
+  }
+  return hipGetLastError();
+}
+
+// The transpose of the whole matrix from its tile transposes (cnmf_csr_transpose_tiles with
+// the same T, G, tl; n_ent entries): rowptrG (G + 1, from 0), colG / valG (n_ent), the
+// entries of a row ordered by cell.  pre: (T, G) int workspace, tot: (G).
+extern "C" hipError_t cnmf_csr_transpose_merge(const int* rowptrT, const int* colT,
+                                               const float* valT, int T, int G, int tl,
+                                               int n_ent, int* pre, int* tot, int* rowptrG,
+                                               int* colG, float* valG, hipStream_t stream) {
+  using namespace cnmf;
+  if (T < 0 || G < 0 || tl < 1 || tl > kCtMaxTile || n_ent < 0 ||
+      (long long)T * tl > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  if (G == 0) return hipSuccess;
+  const dim3 blk(kCtThreads);
+  hipLaunchKernelGGL(ct_gene_prefix_kernel, dim3((G + kCtThreads - 1) / kCtThreads), blk, 0,
+                     stream, rowptrT, T, G, pre, tot);
+  hipLaunchKernelGGL(ct_total_scan_kernel, dim3(1), blk, 0, stream, tot, G, rowptrG);
+  const long long n_seg = (long long)T * G;
+  if (n_seg > 0 && n_ent > 0) {
+    const long long wgs = (n_seg + kCtWaves - 1) / kCtWaves;
+    hipLaunchKernelGGL(ct_merge_kernel, dim3((unsigned)(wgs < kCtMaxGrid ? wgs : kCtMaxGrid)),
+                       blk, 0, stream, rowptrT, G, tl, n_seg, n_ent, pre, rowptrG, colT, valT,
+                       colG, valG);
   }
   return hipGetLastError();
 }

@@ -116,8 +116,18 @@ hipError_t cnmf_sk_run(int side, const int* rowptr, const int* col, const float*
                        float tol, int conv_mode, double* hstate, double* part, int* counter,
                        int* act, int* iters, const int* active, double* loss, double xsum,
                        hipStream_t stream);
+// one KL MU step of R row chunks (c rows each) against one shared S^T, iterate-change rule
+hipError_t cnmf_sk_refit_step(const int* rowptr, const int* col, const float* val,
+                              const float* ST, float* F, long long ldf, int K, int c, int Ls,
+                              int R, float eps, const float* den_vec, float l1, float l2,
+                              float tol, double* part, int* counter, int* act, int* iters,
+                              hipStream_t stream);
 
-// csr_transpose.hip: transposed tile CSRs of a row chunk of a device CSR matrix
+// csr_transpose.hip: transposed tile CSRs of a row chunk of a device CSR matrix, and their
+// merge into the transpose of the whole matrix
+hipError_t cnmf_csr_transpose_merge(const int* rowptrT, const int* colT, const float* valT,
+                                    int T, int G, int tl, int n_ent, int* pre, int* tot,
+                                    int* rowptrG, int* colG, float* valG, hipStream_t stream);
 int cnmf_csr_transpose_max_tile();
 hipError_t cnmf_csr_transpose_tiles(const int* rowptr, const int* col, const float* val, int c,
                                     int G, int tl, int lo, int hi, int* cnt, void* tmp,

@@ -25,6 +25,15 @@
 // block-objective stopping rule is the dense kernel's (last workgroup of the replicate to
 // arrive decides, cdna_hip_programming.md G16).
 //
+// Chunk-batched mode of the usage side (cnmf_sk_refit_step, the KL refit of models/refit.py):
+// "replicate" r is row chunk r of one matrix -- its CSR rows start rowptr + r * row_rs, its
+// usages are the columns [r c, (r + 1) c) of one (K x n) array -- and all chunks gather from
+// one S^T / den_vec.  One launch is one MU step of every chunk whose flag is set, then the
+// iterate-change rule per chunk; with the operand shared the XCD pinning has no purpose, so
+// the blocks interleave over the chunks and two chunks still use every XCD.  A run-time field:
+// registers, scratch and occupancy of every instantiation are what they were without it
+// (profiles/p8_kl_refit.txt), and with it off a launch is bit for bit the former one.
+//
 // Buckets, <KS, NQH> by padded rank K4, and their VGPRs (hipcc
 // -Rpass-analysis=kernel-resource-usage; usage LDS (512 threads) / L2, spectra LDS / L2; no
 // scratch and no AGPRs anywhere but the 256-VGPR usage kernels at K4 = 28 and 32):
@@ -79,6 +88,10 @@ struct SkParams {
   float* num;          // side W: (R, K, Lf)
   int nsteps, loss_entry, loss_exit;
   const float* den_vec;  // (R, K) row sums of S
+  // chunk-batched usage step (a refit: many row chunks against one shared fixed S): replicate
+  // r is chunk r, reads the CSR rows from rowptr + r * row_rs on and gathers from the one
+  // S^T / den_vec (no replicate stride); 0 / 0 everywhere else
+  int chunk, row_rs;
   float l1, l2, tol;
   int conv_mode;
   double* hstate;      // (R, 2)
@@ -211,10 +224,12 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
   extern __shared__ __attribute__((aligned(16))) float sk_lds[];
   // XCD-aware map: replicate r runs on XCD r % 8 (all of its workgroups), its replicates
   // interleaved, so its S^T rows are gathered from one L2
+  // (chunk mode: the operand is shared, so the chunks interleave and R < 8 of them still
+  // spread over every XCD)
   const int b = blockIdx.x, xcd = b & 7, local = b >> 3;
   const int RX = (p.R + 7) >> 3;
-  const int rep = (local % RX) * 8 + xcd;
-  const int grp = local / RX;
+  const int rep = p.chunk ? b % p.R : (local % RX) * 8 + xcd;
+  const int grp = p.chunk ? b / p.R : local / RX;
   if (rep >= p.R || grp >= p.n_groups) return;
   if (p.active && p.active[rep] == 0) return;
   const int tid = threadIdx.x;
@@ -232,7 +247,8 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
   int voff[NQH];                                              // quad offsets in a row
 #pragma unroll
   for (int v = 0; v < NQH; ++v) voff[v] = min(k0 + 4 * v, K4 - 4);
-  const float* __restrict__ ST = p.ST + (long long)rep * p.st_rs;
+  const float* __restrict__ ST = p.ST + (p.chunk ? 0LL : (long long)rep * p.st_rs);
+  const int* __restrict__ rowptr = p.rowptr + (long long)rep * p.row_rs;
   if (LDS) {
     const float4* src = reinterpret_cast<const float4*>(ST);
     float4* dst = reinterpret_cast<float4*>(sk_lds);
@@ -242,7 +258,7 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
     ST = sk_lds;
   }
   float* __restrict__ F = p.F + (long long)rep * p.f_rs + (long long)kb * p.ldf;
-  const float* dv = p.den_vec ? p.den_vec + (long long)rep * K : nullptr;
+  const float* dv = p.den_vec ? p.den_vec + (p.chunk ? 0LL : (long long)rep * K) : nullptr;
   float den[KH];
 #pragma unroll
   for (int k = 0; k < KH; ++k) den[k] = (dv && k0 + k < K) ? dv[k0 + k] : 0.f;
@@ -260,7 +276,7 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
 #pragma unroll
     for (int k = 0; k < KH; ++k) h[k] = k0 + k < K ? F[(long long)(ki + k) * p.ldf + c] : 0.f;
     sk_f2 h2[KH / 2];
-    const int beg = p.rowptr[c], end = p.rowptr[c + 1];
+    const int beg = rowptr[c], end = rowptr[c + 1];
     const int trips = (end - beg + kSkSlots * kSkU - 1) / (kSkSlots * kSkU);
     for (int it = 0; it < n_it; ++it) {
       const bool want_num = !UPD || it < p.nsteps;
@@ -378,7 +394,7 @@ __global__ void __launch_bounds__(LDS ? kSkThreadsL : kSkThreads) sk_kernel(SkPa
 template <int KS, int NQH, int U, bool UPD, bool LDS>
 hipError_t sk_launch(const SkParams& p, hipStream_t s) {
   const int RX = (p.R + 7) / 8;
-  const dim3 grid((unsigned)(8 * RX * p.n_groups));
+  const dim3 grid((unsigned)((p.chunk ? p.R : 8 * RX) * p.n_groups));
   const size_t lds = LDS ? (size_t)p.Ls * 4 * p.K4 : 0;
   if (LDS) {
     static bool attr_done = false;
@@ -475,6 +491,7 @@ extern "C" hipError_t cnmf_sk_run(
   p.den_vec = den_vec; p.l1 = l1; p.l2 = l2; p.tol = tol; p.conv_mode = conv_mode;
   p.hstate = hstate; p.part = part; p.counter = counter; p.act = act; p.iters = iters;
   p.active = active; p.loss = loss; p.xsum = xsum;
+  p.chunk = 0; p.row_rs = 0;
   if (side == 1) {
     if (num == nullptr) return hipErrorInvalidValue;
     return cnmf::sk_launch_u<false>(p, stream);
@@ -483,6 +500,39 @@ extern "C" hipError_t cnmf_sk_run(
       (part != nullptr && conv_mode == 1 && hstate == nullptr) ||
       (nsteps == 0 && loss == nullptr && part == nullptr))
     return hipErrorInvalidValue;
+  return cnmf::sk_launch_u<true>(p, stream);
+}
+
+// Chunk-batched usage step (a refit with the spectra fixed): one KL MU step of every still
+// active chunk of c rows, chunk r = CSR rows [r c, (r + 1) c) of `rowptr` (R c + 1 offsets)
+// and the columns [r c, (r + 1) c) of F (K x ldf), all against the one S^T (Ls x K4) /
+// den_vec (K); then the iterate-change rule per chunk (conv_mode 0): act[r] cleared, iters[r]
+// counted, `part` (R, groups, 4) / `counter` (R) as for cnmf_sk_run.
+extern "C" hipError_t cnmf_sk_refit_step(
+    const int* rowptr, const int* col, const float* val, const float* ST, float* F,
+    long long ldf, int K, int c, int Ls, int R, float eps, const float* den_vec, float l1,
+    float l2, float tol, double* part, int* counter, int* act, int* iters,
+    hipStream_t stream) {
+  if (R <= 0 || c <= 0) return hipSuccess;
+  if (K < 1 || K > cnmf::kSkMaxK || Ls <= 0 || rowptr == nullptr || ST == nullptr ||
+      (reinterpret_cast<uintptr_t>(ST) & 15) != 0 || F == nullptr || den_vec == nullptr ||
+      part == nullptr || counter == nullptr || act == nullptr ||
+      ldf < (long long)R * c)
+    return hipErrorInvalidValue;
+  cnmf::SkParams p;
+  p.rowptr = rowptr; p.col = col; p.val = val;
+  p.ST = ST; p.st_rs = 0;
+  p.F = F; p.f_rs = c; p.ldf = ldf;
+  p.K = K; p.K4 = cnmf_sk_k4(K); p.Lf = c; p.Ls = Ls; p.R = R;
+  p.cols_per_wg = cnmf_sk_cols_per_wg(c, R, Ls, K);
+  p.n_groups = (c + p.cols_per_wg - 1) / p.cols_per_wg;
+  if ((long long)R * p.n_groups > 0x7fffffffLL) return hipErrorInvalidValue;
+  p.eps = eps; p.num = nullptr;
+  p.nsteps = 1; p.loss_entry = 0; p.loss_exit = 0;
+  p.den_vec = den_vec; p.l1 = l1; p.l2 = l2; p.tol = tol; p.conv_mode = 0;
+  p.hstate = nullptr; p.part = part; p.counter = counter; p.act = act; p.iters = iters;
+  p.active = act; p.loss = nullptr; p.xsum = 0.0;
+  p.chunk = 1; p.row_rs = c;
   return cnmf::sk_launch_u<true>(p, stream);
 }
 
