@@ -1,12 +1,14 @@
 // Launcher + C ABI of the fused inner solve (kernels in solve_core.h).  This unit
-// instantiates the streaming variant; solve_res.hip the register-resident one.
+// instantiates the streaming variant for K <= 32; solve_wide.hip the wide streaming ranks,
+// solve_res.hip / solve_res34.hip the register-resident one, solve_mfma.hip,
+// solve_wmfma.hip and solve_pipe*.hip the matrix-core bodies.
 #include "launchers.h"
 #include "solve_core.h"
 
 namespace cnmf {
 hipError_t launch_solve_stream(int K, int algo, const SolveParams& p, int nblocks, int threads,
                                hipStream_t s) {
-  CNMF_SOLVE_K_SWITCH(0)
+  return launch_solve_stream_ranks(K, rank_range<1, 32>{}, algo, p, nblocks, threads, s);
 }
 }  // namespace cnmf
 
@@ -96,8 +98,9 @@ extern "C" hipError_t cnmf_solve(int algo, int K, float* x, long long x_rs, long
   // dispatch" in docs/ARCHITECTURE.md).  Each case checks that kernel's own preconditions
   // -- a failed one is an error, never another kernel -- and derives only what follows from
   // its geometry (tiles, columns per thread, workgroup order).
+  // columns per slice, by the kernels' own rule (solve_slice in solve_core.h)
   const int parts = nsplit > 1 ? nsplit : (coop_split > 1 ? coop_split : 1);
-  const int per = (ncols + parts - 1) / parts;
+  const int per = cnmf::solve_cols_per_slice(ncols, parts);
   // the in-prologue Gram is solve_mfma's; fused operands and launch rounds (reps_per_launch
   // replicates at a time, each round co-resident) the pipelined kernel's: never dropped
   if (gsrc && (kernel != CNMF_SOLVE_mfma || gs_cols < 1)) return hipErrorInvalidValue;

@@ -30,6 +30,8 @@
 // registers (that hoisting spilled hundreds of VGPRs at K >= 7).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
+#include <utility>
 #include "common.h"
 #include "solve_params.h"
 
@@ -329,6 +331,110 @@ __device__ __forceinline__ void emit_planes(const SolveParams& p, int rep, int j
   }
 }
 
+// Columns per slice when a replicate's ncols columns are split over `parts` workgroups
+// (nsplit fixed-step slices or S cooperative ones).  The one rule for the kernels
+// (solve_slice) and for the host's per-kernel capacity checks (cnmf_solve).
+__host__ __device__ constexpr int solve_cols_per_slice(int ncols, int parts) {
+  return (ncols + parts - 1) / parts;
+}
+
+// gridDim.y of every solve launch but the pipelined one: the slices of a replicate
+inline int solve_grid_y(const SolveParams& p) {
+  return p.nsplit > 1 ? p.nsplit : (p.coop_slots ? p.coop_epochs_split : 1);
+}
+
+// Column range [j0, n) of this workgroup: the whole block, one of nsplit fixed-step
+// slices, or one of S cooperative slices (gridDim.y) that still converge together.
+struct SolveSlice {
+  int j0, n;
+  bool coop;
+};
+__device__ __forceinline__ SolveSlice solve_slice(const SolveParams& p) {
+  SolveSlice sl{0, p.ncols, p.coop_slots != nullptr && gridDim.y > 1};
+  if (p.nsplit > 1 || sl.coop) {
+    const int per = solve_cols_per_slice(p.ncols, sl.coop ? (int)gridDim.y : p.nsplit);
+    sl.j0 = min(p.ncols, (int)blockIdx.y * per);
+    sl.n = min(p.ncols, sl.j0 + per);
+  }
+  return sl;
+}
+
+// Stopping rules of every solve body but the pipelined one.  Each body's loop reads
+//   const bool check_conv = p.nsplit <= 1;                  (false: fixed step count)
+//   const bool loss_conv = check_conv && p.conv_mode == 1;  (block objective)
+//   const int every = p.check_every > 0 ? p.check_every : 1;
+//   int epoch = 0, it = 0;  float f_prev = 0.f;  bool have_prev = false;
+//   while (true) {
+//     if (loss_conv && it % every == 0) {            objective rule, conv_mode 1
+//       <q, l partials of f = q - 2 l>
+//       block_sum2(q, l, sred);  float f = q - 2.f * l;
+//       if (coop) { float unused = 0.f;
+//                   if (!coop_sum2(p, rep, epoch++, f, unused, sred)) break; }
+//       if (have_prev && fabsf(f_prev - f) <= p.tol * fabsf(f_prev)) break;
+//       f_prev = f;  have_prev = true;               (a failed exchange leaves f_prev alone)
+//     }
+//     if (it >= p.max_iter) break;
+//     <one sweep, d2 / x2 partials>;  ++it;
+//     if (!check_conv || loss_conv) continue;
+//     block_sum2(d2, x2, sred);                      iterate-change rule, conv_mode 0
+//     if (coop && !coop_sum2(p, rep, epoch++, d2, x2, sred)) break;
+//     if (sqrtf(d2) / (sqrtf(x2) + eps) < p.tol) break;
+//   }
+// These statements stay spelled out in the four loops (solve_kernel's two, solve_mfma,
+// solve_wmfma), and a change to a rule is made in all four: as calls of a shared helper, or
+// with the loop state gathered in a struct, they moved the bodies' register allocation
+// (VGPR counts and spills, one lost occupancy step) or their time
+// (profiles/p9_solve_helpers.txt).
+
+// lin / quad epilogue from this thread's partials: thread 0 of slice 0 stores the totals;
+// the fixed-step slices (nsplit, check_conv false) add theirs to outputs the caller zeroed.
+// The streaming loop of solve_kernel keeps these statements spelled out: the call moved its
+// register allocation too.
+__device__ __forceinline__ void solve_write_linquad(const SolveParams& p, int rep, bool coop,
+                                                    bool check_conv, int& epoch, float lin,
+                                                    float quad, float* sred) {
+  block_sum2(lin, quad, sred);
+  if (coop) (void)coop_sum2(p, rep, epoch++, lin, quad, sred);
+  if (threadIdx.x == 0 && (!coop || blockIdx.y == 0)) {
+    if (check_conv) {
+      if (p.lin_out) p.lin_out[rep] = lin;
+      if (p.quad_out) p.quad_out[rep] = quad;
+    } else {
+      if (p.lin_out) atomicAdd(p.lin_out + rep, lin);
+      if (p.quad_out) atomicAdd(p.quad_out + rep, quad);
+    }
+  }
+}
+
+// Tail of every body: the bf16 planes of the final x, and the step count.
+template <int K>
+__device__ __forceinline__ void solve_finish(const SolveParams& p, int rep, const SolveSlice& sl,
+                                             int it) {
+  if (p.planes) {
+    __syncthreads();   // every thread's final x stores precede the re-read (same block)
+    emit_planes<K>(p, rep, sl.j0, sl.n, gridDim.y <= 1 || blockIdx.y == gridDim.y - 1);
+  }
+  if (p.iters_out && threadIdx.x == 0 && blockIdx.y == 0) p.iters_out[rep] += it;
+}
+
+// Compile-time rank dispatch for the launchers: calls f(std::integral_constant<int, K>)
+// for the K of the list equal to k; hipErrorInvalidValue for a rank the list lacks.
+// rank_range<Lo, Hi, Step> is the list Lo, Lo + Step, ..., Hi.
+template <int... Ks, class F>
+hipError_t dispatch_rank(int k, std::integer_sequence<int, Ks...>, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((k == Ks && ((e = f(std::integral_constant<int, Ks>{})), true)) || ...);
+  return e;
+}
+template <int Lo, int Step, int... I>
+constexpr std::integer_sequence<int, (Lo + Step * I)...> rank_seq(
+    std::integer_sequence<int, I...>) {
+  return {};
+}
+template <int Lo, int Hi, int Step = 1>
+using rank_range =
+    decltype(rank_seq<Lo, Step>(std::make_integer_sequence<int, (Hi - Lo) / Step + 1>{}));
+
 // Row k of the padded LDS Gram into row[KP] (KP/4 broadcast b128 reads).
 #define CNMF_GRAM_ROW(GZ, k, row)                                                                 \
   float row[KP];                                                                                  \
@@ -511,16 +617,9 @@ __global__ __launch_bounds__(solve_block_threads<K>()) void solve_kernel(SolvePa
   const __amdgpu_buffer_rsrc_t rn = rsrc_of(nu);
   const int sx = (int)(p.ldx * 4), sn = (int)(p.ldn * 4);
   const int T = blockDim.x;
-  // Column range of this block: the whole block, one of nsplit fixed-step slices, or one
-  // of S cooperative slices (gridDim.y) that still converge together.
-  int j0 = 0, n = p.ncols;
-  const bool coop = p.coop_slots != nullptr && gridDim.y > 1;
-  if (p.nsplit > 1 || coop) {
-    const int parts = coop ? (int)gridDim.y : p.nsplit;
-    const int per = (p.ncols + parts - 1) / parts;
-    j0 = min(p.ncols, (int)blockIdx.y * per);
-    n = min(p.ncols, j0 + per);
-  }
+  const SolveSlice sl = solve_slice(p);
+  const int j0 = sl.j0, n = sl.n;
+  const bool coop = sl.coop;
   const bool check_conv = p.nsplit <= 1;
   int epoch = 0;
   const bool loss_conv = check_conv && p.conv_mode == 1;
@@ -529,6 +628,7 @@ __global__ __launch_bounds__(solve_block_threads<K>()) void solve_kernel(SolvePa
   float f_prev = 0.f;
   bool have_prev = false;
   int it = 0;
+  // both loops below follow the stopping rules written out above solve_write_linquad
   if constexpr (resident) {
     // Register-resident path: x stays in VGPRs for every iteration and the numerator in
     // LDS (no per-iteration global round trip -- that latency/L2 traffic, not
@@ -588,17 +688,7 @@ __global__ __launch_bounds__(solve_block_threads<K>()) void solve_kernel(SolvePa
       } else {
         CNMF_LINQUAD_GROUP(rg, CNMF_NLDS);
       }
-      block_sum2(lin, quad, sred);
-      if (coop) (void)coop_sum2(p, rep, epoch++, lin, quad, sred);
-      if (threadIdx.x == 0 && (!coop || blockIdx.y == 0)) {
-        if (check_conv) {
-          if (p.lin_out) p.lin_out[rep] = lin;
-          if (p.quad_out) p.quad_out[rep] = quad;
-        } else {  // split columns: caller zeroed the outputs
-          if (p.lin_out) atomicAdd(p.lin_out + rep, lin);
-          if (p.quad_out) atomicAdd(p.quad_out + rep, quad);
-        }
-      }
+      solve_write_linquad(p, rep, coop, check_conv, epoch, lin, quad, sred);
     }
   } else {
     while (true) {
@@ -648,19 +738,14 @@ __global__ __launch_bounds__(solve_block_threads<K>()) void solve_kernel(SolvePa
       }
     }
   }
-  if (p.planes) {
-    __syncthreads();   // every thread's final x stores precede the re-read (same block)
-    emit_planes<K>(p, rep, j0, n, gridDim.y <= 1 || blockIdx.y == gridDim.y - 1);
-  }
-  if (p.iters_out && threadIdx.x == 0 && blockIdx.y == 0) p.iters_out[rep] += it;
+  solve_finish<K>(p, rep, sl, it);
 }
 
 template <int K, int RES>
 hipError_t launch_solve_k(int algo, const SolveParams& p, int nblocks, int threads,
                           hipStream_t s) {
   if (threads > solve_block_threads<K>()) threads = solve_block_threads<K>();
-  const int gy = p.nsplit > 1 ? p.nsplit : (p.coop_slots ? p.coop_epochs_split : 1);
-  const dim3 grid(nblocks, gy);
+  const dim3 grid(nblocks, solve_grid_y(p));
   if (algo == 0)
     hipLaunchKernelGGL((solve_kernel<K, 0, RES>), grid, dim3(threads), 0, s, p);
   else
@@ -668,52 +753,15 @@ hipError_t launch_solve_k(int algo, const SolveParams& p, int nblocks, int threa
   return hipGetLastError();
 }
 
-#define CNMF_SOLVE_K_SWITCH(RES)                                                          \
-  switch (K) {                                                                            \
-    case 1: return launch_solve_k<1, RES>(algo, p, nblocks, threads, s);                  \
-    case 2: return launch_solve_k<2, RES>(algo, p, nblocks, threads, s);                  \
-    case 3: return launch_solve_k<3, RES>(algo, p, nblocks, threads, s);                  \
-    case 4: return launch_solve_k<4, RES>(algo, p, nblocks, threads, s);                  \
-    case 5: return launch_solve_k<5, RES>(algo, p, nblocks, threads, s);                  \
-    case 6: return launch_solve_k<6, RES>(algo, p, nblocks, threads, s);                  \
-    case 7: return launch_solve_k<7, RES>(algo, p, nblocks, threads, s);                  \
-    case 8: return launch_solve_k<8, RES>(algo, p, nblocks, threads, s);                  \
-    case 9: return launch_solve_k<9, RES>(algo, p, nblocks, threads, s);                  \
-    case 10: return launch_solve_k<10, RES>(algo, p, nblocks, threads, s);                \
-    case 11: return launch_solve_k<11, RES>(algo, p, nblocks, threads, s);                \
-    case 12: return launch_solve_k<12, RES>(algo, p, nblocks, threads, s);                \
-    case 13: return launch_solve_k<13, RES>(algo, p, nblocks, threads, s);                \
-    case 14: return launch_solve_k<14, RES>(algo, p, nblocks, threads, s);                \
-    case 15: return launch_solve_k<15, RES>(algo, p, nblocks, threads, s);                \
-    case 16: return launch_solve_k<16, RES>(algo, p, nblocks, threads, s);                \
-    case 17: return launch_solve_k<17, RES>(algo, p, nblocks, threads, s);                \
-    case 18: return launch_solve_k<18, RES>(algo, p, nblocks, threads, s);                \
-    case 19: return launch_solve_k<19, RES>(algo, p, nblocks, threads, s);                \
-    case 20: return launch_solve_k<20, RES>(algo, p, nblocks, threads, s);                \
-    case 21: return launch_solve_k<21, RES>(algo, p, nblocks, threads, s);                \
-    case 22: return launch_solve_k<22, RES>(algo, p, nblocks, threads, s);                \
-    case 23: return launch_solve_k<23, RES>(algo, p, nblocks, threads, s);                \
-    case 24: return launch_solve_k<24, RES>(algo, p, nblocks, threads, s);                \
-    case 25: return launch_solve_k<25, RES>(algo, p, nblocks, threads, s);                \
-    case 26: return launch_solve_k<26, RES>(algo, p, nblocks, threads, s);                \
-    case 27: return launch_solve_k<27, RES>(algo, p, nblocks, threads, s);                \
-    case 28: return launch_solve_k<28, RES>(algo, p, nblocks, threads, s);                \
-    case 29: return launch_solve_k<29, RES>(algo, p, nblocks, threads, s);                \
-    case 30: return launch_solve_k<30, RES>(algo, p, nblocks, threads, s);                \
-    case 31: return launch_solve_k<31, RES>(algo, p, nblocks, threads, s);                \
-    case 32: return launch_solve_k<32, RES>(algo, p, nblocks, threads, s);                \
-    default: return hipErrorInvalidValue;                                                 \
-  }
-
-// wide ranks (K padded to a multiple of 8 by the NMF engine), streaming variant only
-#define CNMF_SOLVE_WIDE_SWITCH()                                                          \
-  switch (K) {                                                                            \
-    case 40: return launch_solve_k<40, 0>(algo, p, nblocks, threads, s);                  \
-    case 48: return launch_solve_k<48, 0>(algo, p, nblocks, threads, s);                  \
-    case 56: return launch_solve_k<56, 0>(algo, p, nblocks, threads, s);                  \
-    case 64: return launch_solve_k<64, 0>(algo, p, nblocks, threads, s);                  \
-    default: return hipErrorInvalidValue;                                                 \
-  }
+// Streaming launch for the ranks of the list Ks (1..32 in solve.hip; the padded wide ranks
+// 40..64, multiples of 8, in solve_wide.hip)
+template <class Ks>
+hipError_t launch_solve_stream_ranks(int K, Ks, int algo, const SolveParams& p, int nblocks,
+                                     int threads, hipStream_t s) {
+  return dispatch_rank(K, Ks{}, [&](auto k) {
+    return launch_solve_k<decltype(k)::value, 0>(algo, p, nblocks, threads, s);
+  });
+}
 
 // register-resident variant: K <= kResidentMaxK, U <= res_max_cols(K) columns per thread
 constexpr int kResidentMaxK = 24;
@@ -728,35 +776,13 @@ hipError_t launch_solve_res_ku(int algo, const SolveParams& p, int nblocks, int 
     return launch_solve_k<K, U>(algo, p, nblocks, threads, s);
   }
 }
-
-#define CNMF_SOLVE_RES_SWITCH(U)                                                          \
-  switch (K) {                                                                            \
-    case 1: return launch_solve_res_ku<1, U>(algo, p, nblocks, threads, s);               \
-    case 2: return launch_solve_res_ku<2, U>(algo, p, nblocks, threads, s);               \
-    case 3: return launch_solve_res_ku<3, U>(algo, p, nblocks, threads, s);               \
-    case 4: return launch_solve_res_ku<4, U>(algo, p, nblocks, threads, s);               \
-    case 5: return launch_solve_res_ku<5, U>(algo, p, nblocks, threads, s);               \
-    case 6: return launch_solve_res_ku<6, U>(algo, p, nblocks, threads, s);               \
-    case 7: return launch_solve_res_ku<7, U>(algo, p, nblocks, threads, s);               \
-    case 8: return launch_solve_res_ku<8, U>(algo, p, nblocks, threads, s);               \
-    case 9: return launch_solve_res_ku<9, U>(algo, p, nblocks, threads, s);               \
-    case 10: return launch_solve_res_ku<10, U>(algo, p, nblocks, threads, s);             \
-    case 11: return launch_solve_res_ku<11, U>(algo, p, nblocks, threads, s);             \
-    case 12: return launch_solve_res_ku<12, U>(algo, p, nblocks, threads, s);             \
-    case 13: return launch_solve_res_ku<13, U>(algo, p, nblocks, threads, s);             \
-    case 14: return launch_solve_res_ku<14, U>(algo, p, nblocks, threads, s);             \
-    case 15: return launch_solve_res_ku<15, U>(algo, p, nblocks, threads, s);             \
-    case 16: return launch_solve_res_ku<16, U>(algo, p, nblocks, threads, s);             \
-    case 17: return launch_solve_res_ku<17, U>(algo, p, nblocks, threads, s);             \
-    case 18: return launch_solve_res_ku<18, U>(algo, p, nblocks, threads, s);             \
-    case 19: return launch_solve_res_ku<19, U>(algo, p, nblocks, threads, s);             \
-    case 20: return launch_solve_res_ku<20, U>(algo, p, nblocks, threads, s);             \
-    case 21: return launch_solve_res_ku<21, U>(algo, p, nblocks, threads, s);             \
-    case 22: return launch_solve_res_ku<22, U>(algo, p, nblocks, threads, s);             \
-    case 23: return launch_solve_res_ku<23, U>(algo, p, nblocks, threads, s);             \
-    case 24: return launch_solve_res_ku<24, U>(algo, p, nblocks, threads, s);             \
-    default: return hipErrorInvalidValue;                                                 \
-  }
+template <int U>
+hipError_t launch_solve_res_u(int K, int algo, const SolveParams& p, int nblocks, int threads,
+                              hipStream_t s) {
+  return dispatch_rank(K, rank_range<1, kResidentMaxK>{}, [&](auto k) {
+    return launch_solve_res_ku<decltype(k)::value, U>(algo, p, nblocks, threads, s);
+  });
+}
 
 // one per translation unit (solve.hip / solve_res.hip / solve_res34.hip build in parallel)
 hipError_t launch_solve_stream(int K, int algo, const SolveParams& p, int nblocks, int threads,

@@ -113,14 +113,9 @@ void solve_mfma_kernel(SolveParams p, int T) {
     }
   }
 
-  int j0 = 0, n = p.ncols;
-  const bool coop = p.coop_slots != nullptr && gridDim.y > 1;
-  if (p.nsplit > 1 || coop) {
-    const int parts = coop ? (int)gridDim.y : p.nsplit;
-    const int per = (p.ncols + parts - 1) / parts;
-    j0 = min(p.ncols, (int)blockIdx.y * per);
-    n = min(p.ncols, j0 + per);
-  }
+  const SolveSlice sl = solve_slice(p);
+  const int j0 = sl.j0, n = sl.n;
+  const bool coop = sl.coop;
 
   // x and the (l1_num-shifted) numerator of this lane's columns, B layout.  Buffer
   // accesses: 32-bit offsets computed at each use (col0 is re-derived through an opaque
@@ -162,6 +157,7 @@ void solve_mfma_kernel(SolveParams p, int T) {
   float lin_p = 0.f, quad_p = 0.f;
   bool lq_valid = false;
 
+  // the stopping rules are those written out above solve_write_linquad in solve_core.h
   while (true) {
     if (loss_conv && it % every == 0) {
       // objective x^T Gram x + l2 |x|^2 - 2 (numer - l1) . x, accumulated as four plain
@@ -295,28 +291,14 @@ void solve_mfma_kernel(SolveParams p, int T) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    block_sum2(lin, quad, sred);
-    if (coop) (void)coop_sum2(p, rep, epoch++, lin, quad, sred);
-    if (threadIdx.x == 0 && (!coop || blockIdx.y == 0)) {
-      if (check_conv) {
-        if (p.lin_out) p.lin_out[rep] = lin;
-        if (p.quad_out) p.quad_out[rep] = quad;
-      } else {  // split columns: caller zeroed the outputs
-        if (p.lin_out) atomicAdd(p.lin_out + rep, lin);
-        if (p.quad_out) atomicAdd(p.quad_out + rep, quad);
-      }
-    }
+    solve_write_linquad(p, rep, coop, check_conv, epoch, lin, quad, sred);
   }
-  if (p.planes) {
-    __syncthreads();   // every lane's final x stores precede the re-read (same block)
-    emit_planes<K>(p, rep, j0, n, gridDim.y <= 1 || blockIdx.y == gridDim.y - 1);
-  }
-  if (p.iters_out && threadIdx.x == 0 && blockIdx.y == 0) p.iters_out[rep] += it;
+  solve_finish<K>(p, rep, sl, it);
 }
 
 template <int K>
 static hipError_t launch_mfma_k(const SolveParams& p, int nblocks, int T, hipStream_t s) {
-  const int gy = p.nsplit > 1 ? p.nsplit : (p.coop_slots ? p.coop_epochs_split : 1);
+  const int gy = solve_grid_y(p);
   if (p.nsplit <= 1 && p.conv_mode == 0)
     hipLaunchKernelGGL((solve_mfma_kernel<K, mfma_tile_max(K), true>), dim3(nblocks, gy),
                        dim3(64 * kMfmaWaves), 0, s, p, T);
@@ -327,25 +309,9 @@ static hipError_t launch_mfma_k(const SolveParams& p, int nblocks, int T, hipStr
 }
 
 hipError_t launch_solve_mfma(int K, const SolveParams& p, int nblocks, int T, hipStream_t s) {
-  switch (K) {
-    case 1: return launch_mfma_k<1>(p, nblocks, T, s);
-    case 2: return launch_mfma_k<2>(p, nblocks, T, s);
-    case 3: return launch_mfma_k<3>(p, nblocks, T, s);
-    case 4: return launch_mfma_k<4>(p, nblocks, T, s);
-    case 5: return launch_mfma_k<5>(p, nblocks, T, s);
-    case 6: return launch_mfma_k<6>(p, nblocks, T, s);
-    case 7: return launch_mfma_k<7>(p, nblocks, T, s);
-    case 8: return launch_mfma_k<8>(p, nblocks, T, s);
-    case 9: return launch_mfma_k<9>(p, nblocks, T, s);
-    case 10: return launch_mfma_k<10>(p, nblocks, T, s);
-    case 11: return launch_mfma_k<11>(p, nblocks, T, s);
-    case 12: return launch_mfma_k<12>(p, nblocks, T, s);
-    case 13: return launch_mfma_k<13>(p, nblocks, T, s);
-    case 14: return launch_mfma_k<14>(p, nblocks, T, s);
-    case 15: return launch_mfma_k<15>(p, nblocks, T, s);
-    case 16: return launch_mfma_k<16>(p, nblocks, T, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_rank(K, rank_range<1, 16>{}, [&](auto k) {
+    return launch_mfma_k<decltype(k)::value>(p, nblocks, T, s);
+  });
 }
 
 }  // namespace cnmf

@@ -1,5 +1,6 @@
-// Parameter block shared by the streaming (solve.hip) and register-resident
-// (solve_reg.hip) fused solve kernels.
+// Parameter block shared by every fused solve kernel: streaming (solve.hip,
+// solve_wide.hip), register-resident (solve_res.hip, solve_res34.hip) and matrix-core
+// (solve_mfma.hip, solve_wmfma.hip, solve_pipe*.hip).
 #pragma once
 
 namespace cnmf {

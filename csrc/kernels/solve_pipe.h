@@ -707,4 +707,13 @@ static hipError_t launch_pipe_k(const SolveParams& p, int nblocks, int T, int pl
   return hipErrorInvalidValue;
 }
 
+// the ranks of one translation unit (solve_pipe.hip and its band units b2 / b3 / b4)
+template <class Ks>
+static hipError_t launch_pipe_ranks(int K, Ks, const SolveParams& p, int nblocks, int T, int pl_n,
+                                    hipStream_t s) {
+  return dispatch_rank(K, Ks{}, [&](auto k) {
+    return launch_pipe_k<decltype(k)::value>(p, nblocks, T, pl_n, s);
+  });
+}
+
 }  // namespace cnmf

@@ -11,23 +11,14 @@ hipError_t launch_solve_pipe_b3(int K, const SolveParams& p, int nblocks, int T,
 hipError_t launch_solve_pipe_b4(int K, const SolveParams& p, int nblocks, int T, int pl_n,
                                 hipStream_t s);
 
-#define CNMF_PIPE_CASE(KK) \
-  case KK: return launch_pipe_k<KK>(p, nblocks, T, pl_n, s);
 hipError_t launch_solve_pipe(int K, const SolveParams& p, int nblocks, int T, int pl_n,
                              hipStream_t s) {
   if (K < 1 || T < 1 || T > pipe_tile_max(K)) return hipErrorInvalidValue;
   if (K > 32) return launch_solve_pipe_b4(K, p, nblocks, T, pl_n, s);
   if (K > 24) return launch_solve_pipe_b3(K, p, nblocks, T, pl_n, s);
   if (K > 16) return launch_solve_pipe_b2(K, p, nblocks, T, pl_n, s);
-  switch (K) {
-    CNMF_PIPE_CASE(1) CNMF_PIPE_CASE(2) CNMF_PIPE_CASE(3) CNMF_PIPE_CASE(4)
-    CNMF_PIPE_CASE(5) CNMF_PIPE_CASE(6) CNMF_PIPE_CASE(7) CNMF_PIPE_CASE(8)
-    CNMF_PIPE_CASE(9) CNMF_PIPE_CASE(10) CNMF_PIPE_CASE(11) CNMF_PIPE_CASE(12)
-    CNMF_PIPE_CASE(13) CNMF_PIPE_CASE(14) CNMF_PIPE_CASE(15) CNMF_PIPE_CASE(16)
-    default: return hipErrorInvalidValue;
-  }
+  return launch_pipe_ranks(K, rank_range<1, 16>{}, p, nblocks, T, pl_n, s);
 }
-#undef CNMF_PIPE_CASE
 }  // namespace cnmf
 
 // ranks with a pipelined instantiation: 1..32 and the padded wide ranks 40..64

@@ -4,12 +4,6 @@
 namespace cnmf {
 hipError_t launch_solve_pipe_b4(int K, const SolveParams& p, int nblocks, int T, int pl_n,
                                 hipStream_t s) {
-  switch (K) {
-    case 40: return launch_pipe_k<40>(p, nblocks, T, pl_n, s);
-    case 48: return launch_pipe_k<48>(p, nblocks, T, pl_n, s);
-    case 56: return launch_pipe_k<56>(p, nblocks, T, pl_n, s);
-    case 64: return launch_pipe_k<64>(p, nblocks, T, pl_n, s);
-    default: return hipErrorInvalidValue;
-  }
+  return launch_pipe_ranks(K, rank_range<40, 64, 8>{}, p, nblocks, T, pl_n, s);
 }
 }  // namespace cnmf

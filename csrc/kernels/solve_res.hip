@@ -5,8 +5,8 @@
 namespace cnmf {
 hipError_t launch_solve_resident(int K, int U, int algo, const SolveParams& p, int nblocks,
                                  int threads, hipStream_t s) {
-  if (U == 1) { CNMF_SOLVE_RES_SWITCH(1) }
-  if (U == 2) { CNMF_SOLVE_RES_SWITCH(2) }
+  if (U == 1) return launch_solve_res_u<1>(K, algo, p, nblocks, threads, s);
+  if (U == 2) return launch_solve_res_u<2>(K, algo, p, nblocks, threads, s);
   return launch_solve_resident34(K, U, algo, p, nblocks, threads, s);
 }
 }  // namespace cnmf

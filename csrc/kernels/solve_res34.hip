@@ -5,8 +5,8 @@
 namespace cnmf {
 hipError_t launch_solve_resident34(int K, int U, int algo, const SolveParams& p, int nblocks,
                                    int threads, hipStream_t s) {
-  if (U == 3) { CNMF_SOLVE_RES_SWITCH(3) }
-  if (U == 4) { CNMF_SOLVE_RES_SWITCH(4) }
+  if (U == 3) return launch_solve_res_u<3>(K, algo, p, nblocks, threads, s);
+  if (U == 4) return launch_solve_res_u<4>(K, algo, p, nblocks, threads, s);
   return hipErrorInvalidValue;
 }
 }  // namespace cnmf

@@ -6,6 +6,6 @@
 namespace cnmf {
 hipError_t launch_solve_wide(int K, int algo, const SolveParams& p, int nblocks, int threads,
                              hipStream_t s) {
-  CNMF_SOLVE_WIDE_SWITCH()
+  return launch_solve_stream_ranks(K, rank_range<40, 64, 8>{}, algo, p, nblocks, threads, s);
 }
 }  // namespace cnmf

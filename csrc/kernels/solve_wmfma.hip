@@ -166,14 +166,9 @@ __global__ __launch_bounds__(64 * kWideWaves) void solve_wmfma_kernel(SolveParam
     else wm_apply<K>(sA, lane, xr_, acc_);
   };
 
-  int j0 = 0, n = p.ncols;
-  const bool coop = p.coop_slots != nullptr && gridDim.y > 1;
-  if (p.nsplit > 1 || coop) {
-    const int parts = coop ? (int)gridDim.y : p.nsplit;
-    const int per = (p.ncols + parts - 1) / parts;
-    j0 = min(p.ncols, (int)blockIdx.y * per);
-    n = min(p.ncols, j0 + per);
-  }
+  const SolveSlice sl = solve_slice(p);
+  const int j0 = sl.j0, n = sl.n;
+  const bool coop = sl.coop;
   const int ntile = (n - j0 + 15) / 16;
   const __amdgpu_buffer_rsrc_t rx = rsrc_of(x);
   const __amdgpu_buffer_rsrc_t rn = rsrc_of(nu);
@@ -224,6 +219,7 @@ __global__ __launch_bounds__(64 * kWideWaves) void solve_wmfma_kernel(SolveParam
   int epoch = 0, it = 0;
   float f_prev = 0.f;
   bool have_prev = false;
+  // the stopping rules are those written out above solve_write_linquad in solve_core.h
   while (true) {
     if (loss_conv && it % every == 0) {
       float qd, xx, ln, sxs;
@@ -276,29 +272,14 @@ __global__ __launch_bounds__(64 * kWideWaves) void solve_wmfma_kernel(SolveParam
     __syncthreads();   // the lanes' final x stores precede the re-read (same block)
     float qd, xx, ln, sxs;
     objective(false, qd, xx, ln, sxs);   // lin = <raw numerator, x>, quad = x^T Gram x
-    float lin = ln, quad = qd;
-    block_sum2(lin, quad, sred);
-    if (coop) (void)coop_sum2(p, rep, epoch++, lin, quad, sred);
-    if (threadIdx.x == 0 && (!coop || blockIdx.y == 0)) {
-      if (check_conv) {
-        if (p.lin_out) p.lin_out[rep] = lin;
-        if (p.quad_out) p.quad_out[rep] = quad;
-      } else {  // split columns: caller zeroed the outputs
-        if (p.lin_out) atomicAdd(p.lin_out + rep, lin);
-        if (p.quad_out) atomicAdd(p.quad_out + rep, quad);
-      }
-    }
+    solve_write_linquad(p, rep, coop, check_conv, epoch, ln, qd, sred);
   }
-  if (p.planes) {
-    __syncthreads();
-    emit_planes<K>(p, rep, j0, n, gridDim.y <= 1 || blockIdx.y == gridDim.y - 1);
-  }
-  if (p.iters_out && threadIdx.x == 0 && blockIdx.y == 0) p.iters_out[rep] += it;
+  solve_finish<K>(p, rep, sl, it);
 }
 
 template <int K, bool BF>
 static hipError_t launch_wmfma_kb(const SolveParams& p, int nblocks, hipStream_t s) {
-  const int gy = p.nsplit > 1 ? p.nsplit : (p.coop_slots ? p.coop_epochs_split : 1);
+  const int gy = solve_grid_y(p);
   if (p.nsplit <= 1 && p.conv_mode == 0)
     hipLaunchKernelGGL((solve_wmfma_kernel<K, true, BF>), dim3(nblocks, gy),
                        dim3(64 * kWideWaves), 0, s, p);
@@ -316,13 +297,9 @@ static hipError_t launch_wmfma_k(const SolveParams& p, int nblocks, bool bf16, h
 }
 
 hipError_t launch_solve_wmfma(int K, const SolveParams& p, int nblocks, bool bf16, hipStream_t s) {
-  switch (K) {
-    case 80: return launch_wmfma_k<80>(p, nblocks, bf16, s);
-    case 96: return launch_wmfma_k<96>(p, nblocks, bf16, s);
-    case 112: return launch_wmfma_k<112>(p, nblocks, bf16, s);
-    case 128: return launch_wmfma_k<128>(p, nblocks, bf16, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_rank(K, rank_range<80, 128, 16>{}, [&](auto k) {
+    return launch_wmfma_k<decltype(k)::value>(p, nblocks, bf16, s);
+  });
 }
 
 }  // namespace cnmf
