@@ -15,6 +15,7 @@ import contextlib
 import math
 import os
 import threading
+import time
 from typing import NamedTuple
 
 import numpy as np
@@ -1934,6 +1935,93 @@ def seg_median(S: torch.Tensor, rank: np.ndarray, k: int) -> torch.Tensor | None
     _hip.seg_median(S.data_ptr(), S.stride(0), n, G, perm_t.data_ptr(), seg_t.data_ptr(), k,
                     out.data_ptr(), out.stride(0), _stream_ptr(S))
     return out
+
+
+MI_SORT_ELEMENTS = 1 << 23       # sort-buffer bound of mi_cd: about 40 bytes per element
+
+
+def mi_cd(Xp: torch.Tensor, codes, n_neighbors: int = 3, return_counts: bool = False,
+          feature_block: int | None = None, timings: dict | None = None):
+    """Ross (2014) mutual information of every column of the prepared float64 matrix ``Xp``
+    (n, G) against the integer class ``codes`` (n,), before the clamp at 0: ``mi`` (G,)
+    float64 on Xp's device, or ``(mi, m)`` with the neighbour counts ``m`` (n, G) int32 (0 on
+    rows whose class occurs once) when ``return_counts``.  The contract is
+    :func:`reference.mi_cd`, which is also the CPU path.
+
+    GPU (mi_cd.hip): the features go through in blocks of ``feature_block`` (default: as many
+    as keep a block at ``MI_SORT_ELEMENTS`` values, so the sort buffers do not grow with G).
+    Per block ``torch.sort`` orders the values and then, stably, the permuted class codes;
+    the kernel takes one point per thread and the per-feature sums are formed in a fixed
+    order, so the result does not depend on the block size or the run.  ``timings``: a dict
+    that receives the synchronised ``sort`` and ``kernel`` seconds (benchmarks only)."""
+    nn = int(n_neighbors)
+    if not 1 <= nn <= reference.MI_MAX_NEIGHBORS:
+        raise ValueError(f"mi_cd: n_neighbors must be in 1..{reference.MI_MAX_NEIGHBORS}")
+    if not isinstance(Xp, torch.Tensor) or Xp.dtype != torch.float64 or Xp.dim() != 2:
+        raise ValueError("mi_cd: a 2-D float64 tensor is required")
+    n, G = Xp.shape
+    codes = np.asarray(codes.cpu() if isinstance(codes, torch.Tensor) else codes).reshape(-1)
+    if codes.shape[0] != n or codes.dtype.kind not in "iu":
+        raise ValueError("mi_cd: one integer code per row is required")
+    if feature_block is not None and int(feature_block) < 1:
+        raise ValueError("mi_cd: feature_block must be positive")
+    if not bool(torch.isfinite(Xp).all()):
+        raise ValueError("mi_cd: non-finite input")
+    if not use_native(Xp):
+        mi, m = reference.mi_cd(Xp.cpu().numpy(), codes, nn)
+        mi_t = torch.from_numpy(mi).to(Xp.device)
+        return (mi_t, torch.from_numpy(m).to(Xp.device)) if return_counts else mi_t
+    dev = Xp.device
+    keep, _, const = reference.mi_class_terms(codes, nn)
+    n_kept = int(keep.sum())
+    mi = torch.zeros(G, dtype=torch.float64, device=dev)
+    m_out = torch.zeros((n, G), dtype=torch.int32, device=dev) if return_counts else None
+    if n_kept == 0 or G == 0:
+        return (mi, m_out) if return_counts else mi
+    if n_kept > (1 << 30):
+        raise ValueError("mi_cd: at most 2^30 rows")
+    rows = np.flatnonzero(keep)
+    ck = np.unique(codes[keep], return_inverse=True)[1].reshape(-1).astype(np.int32)
+    cnt = np.bincount(ck)
+    seg = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)).to(dev)
+    cid = torch.from_numpy(np.repeat(np.arange(cnt.size, dtype=np.int32), cnt)).to(dev)
+    code_t = torch.from_numpy(ck).to(dev)
+    rowmap = torch.from_numpy(rows.astype(np.int32)).to(dev)
+    psi = torch.from_numpy(reference.mi_psi_table(n_kept)).to(dev)
+    Xk = Xp if n_kept == n else Xp[torch.from_numpy(rows).to(dev)]
+    tile = int(_hip.mi_cd_tile())
+    tiles = (n_kept + tile - 1) // tile
+    fb = int(feature_block) if feature_block is not None else MI_SORT_ELEMENTS // n_kept
+    fb = max(1, min(fb, G, 65535))
+    part = torch.empty((fb, tiles), dtype=torch.float64, device=dev)
+    total = torch.empty(G, dtype=torch.float64, device=dev)
+    stream = _stream_ptr(Xp)
+    t_sort = t_kern = 0.0
+
+    def lap():      # a synchronised clock, only when the caller asked for timings
+        if timings is None:
+            return 0.0
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    for f0 in range(0, G, fb):
+        f1 = min(G, f0 + fb)
+        t0 = lap()
+        vals, perm = torch.sort(Xk[:, f0:f1].t().contiguous(), dim=1)
+        ranks = torch.sort(code_t[perm], dim=1, stable=True).indices
+        t1 = lap()
+        _hip.mi_cd(vals.data_ptr(), perm.data_ptr(), ranks.data_ptr(), cid.data_ptr(),
+                   seg.data_ptr(), psi.data_ptr(), f1 - f0, n_kept, nn, part.data_ptr(), tiles,
+                   total[f0:f1].data_ptr(),
+                   m_out[:, f0:f1].data_ptr() if return_counts else 0,
+                   m_out.stride(0) if return_counts else 0, rowmap.data_ptr(), stream)
+        t_sort += t1 - t0
+        t_kern += lap() - t1
+    if timings is not None:
+        timings["sort"] = t_sort
+        timings["kernel"] = t_kern
+    mi = const - total / n_kept
+    return (mi, m_out) if return_counts else mi
 
 
 def kmeanspp_fused_ok(X: torch.Tensor, M: int) -> bool:

@@ -511,3 +511,156 @@ def kl_refit(csr, HT, W, chunk_size, max_iter, tol, l1=0.0, l2=0.0, eps=1e-16, i
         HT[:, a:b] = h
         if iters is not None:
             iters[ci] += steps
+
+
+# ---------------------------------------------------------------------------------------
+# Mutual information of continuous features against a discrete target (Ross 2014), as
+# scikit-learn 1.7's mutual_info_classif computes it on a dense matrix
+# (docs/ARCHITECTURE.md "Mutual information").  CPU implementation and oracle of mi_cd.hip.
+
+MI_MAX_NEIGHBORS = 8
+
+
+def _mi_rng(random_state):
+    """sklearn's check_random_state: None -> numpy's global RandomState, an int -> a fresh
+    RandomState, a RandomState -> itself."""
+    if random_state is None or random_state is np.random:
+        return np.random.mtrand._rand
+    if isinstance(random_state, np.random.RandomState):
+        return random_state
+    return np.random.RandomState(int(random_state))
+
+
+def mi_prepare(X, random_state=None, row_block: int = 4096) -> np.ndarray:
+    """The float64 matrix scikit-learn's ``_estimate_mi`` hands to its per-feature
+    estimator, bit for bit: every column divided by its ``nanstd`` (1 where that is below
+    10 eps), then ``1e-10 * max(1, mean|x|) * N(0, 1)`` noise added.  The noise is drawn
+    row-major in blocks of ``row_block`` rows, which is the same RandomState stream as one
+    draw of the whole matrix, without a second (n, G) array.
+
+    The result is column-major.  scikit-learn takes the two column statistics on
+    ``X[:, mask]``, which numpy returns column-major, so every column is reduced pairwise
+    over contiguous memory; the same reductions of a row-major matrix differ in the last
+    bit, which moves a neighbour count wherever a squared distance sits on its radius."""
+    X = np.array(X, dtype=np.float64, order="F")        # a copy, like copy=True
+    if X.ndim != 2:
+        raise ValueError("mi_prepare: a 2-D matrix is required")
+    n, G = X.shape
+    std = np.nanstd(X, axis=0)
+    std[std < 10 * np.finfo(np.float64).eps] = 1.0
+    X /= std
+    scale = 1e-10 * np.maximum(1, np.mean(np.abs(X), axis=0))
+    rng = _mi_rng(random_state)
+    step = max(1, int(row_block))
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        X[a:b] += scale * rng.standard_normal(size=(b - a, G))
+    return X
+
+
+def mi_class_terms(codes, n_neighbors: int):
+    """The feature-independent part of the estimator for integer class ``codes`` (n,):
+    (keep, counts, const) with ``keep`` the mask of points whose class has >= 2 members,
+    ``counts`` the class size of every kept point and
+    ``const = psi(n') + mean psi(k_i) - mean psi(N_i)``, k_i = min(n_neighbors, N_i - 1)."""
+    from scipy.special import digamma
+
+    codes = np.asarray(codes)
+    _, inv, cnt = np.unique(codes, return_inverse=True, return_counts=True)
+    size = cnt[inv.reshape(-1)]
+    keep = size > 1
+    counts = size[keep]
+    n_kept = int(keep.sum())
+    if n_kept == 0:
+        return keep, counts, 0.0
+    k_all = np.minimum(int(n_neighbors), counts - 1)
+    const = (digamma(n_kept) + np.mean(digamma(k_all.astype(np.float64)))
+             - np.mean(digamma(counts.astype(np.float64))))
+    return keep, counts, float(const)
+
+
+def mi_psi_table(n: int) -> np.ndarray:
+    """digamma(1..n) in float64 (entry m - 1 is psi(m)): what both backends add."""
+    from scipy.special import digamma
+
+    return digamma(np.arange(1, int(n) + 1, dtype=np.float64))
+
+
+def _mi_reach(v, g, rad2, right: bool):
+    """Per point the last (right) / first (left) sorted index j, outward from its own rank
+    g, with fl((v[j] - v[g])^2) <= rad2: a vectorised bisection (the predicate holds at g
+    and is monotone outward)."""
+    n = v.shape[0]
+    ok = g.copy()
+    bad = np.full(n, n if right else -1, dtype=np.int64)
+    vg = v[g]
+    while True:
+        open_ = np.abs(bad - ok) > 1
+        if not open_.any():
+            return ok
+        mid = (ok + bad) // 2
+        d = v[np.clip(mid, 0, n - 1)] - vg
+        hold = open_ & (d * d <= rad2)
+        ok = np.where(hold, mid, ok)
+        bad = np.where(open_ & ~hold, mid, bad)
+
+
+def mi_cd(Xp, codes, n_neighbors: int = 3):
+    """(mi (G,) float64, m (n, G) int32) of the prepared float64 matrix ``Xp`` (n, G)
+    against the integer class ``codes`` (n,).  Points whose class occurs once are dropped
+    (m = 0 there).  For a kept point i of a class of N_i points: k_i = min(n_neighbors,
+    N_i - 1), r_i = the distance |c_j - c_i| to its k_i-th nearest neighbour of the class,
+    radius_i = nextafter(r_i, 0), and m_i counts the kept points j of every class, i
+    included, with fl((c_j - c_i)^2) <= fl(radius_i^2).  mi = psi(n') + mean psi(k_i) -
+    mean psi(N_i) - mean psi(m_i), before the clamp at 0 that the caller applies
+    (models.mi).  Distances are exact differences for every class size; scikit-learn's
+    brute-force neighbour search for classes of 3 to 7 points is not imitated."""
+    Xp = np.asarray(Xp)
+    if Xp.dtype != np.float64 or Xp.ndim != 2:
+        raise ValueError("mi_cd: a 2-D float64 matrix is required")
+    nn = int(n_neighbors)
+    if not 1 <= nn <= MI_MAX_NEIGHBORS:
+        raise ValueError(f"mi_cd: n_neighbors must be in 1..{MI_MAX_NEIGHBORS}")
+    if not np.isfinite(Xp).all():
+        raise ValueError("mi_cd: non-finite input")
+    n, G = Xp.shape
+    codes = np.asarray(codes).reshape(-1)
+    if codes.shape[0] != n:
+        raise ValueError("mi_cd: one code per row is required")
+    keep, counts, const = mi_class_terms(codes, nn)
+    mi = np.zeros(G, dtype=np.float64)
+    m_all = np.zeros((n, G), dtype=np.int32)
+    n_kept = int(keep.sum())
+    if n_kept == 0:
+        return mi, m_all
+    rows = np.flatnonzero(keep)
+    ck = codes[keep]
+    k_all = np.minimum(nn, counts - 1)
+    pos = np.arange(n_kept)
+    psi = mi_psi_table(n_kept)
+    for f in range(G):
+        c = Xp[keep, f]
+        order = np.argsort(c, kind="stable")
+        v = c[order]
+        cls = ck[order]
+        ranks = np.argsort(cls, kind="stable")          # class order -> sorted position
+        cs = cls[ranks]
+        start = np.flatnonzero(np.r_[True, cs[1:] != cs[:-1]])
+        a = np.repeat(start, np.diff(np.r_[start, n_kept]))     # segment bounds per slot
+        b = np.repeat(np.r_[start[1:], n_kept], np.diff(np.r_[start, n_kept]))
+        vq = v[ranks]
+        D = np.full((n_kept, 2 * nn), np.inf)
+        for j in range(1, nn + 1):
+            left = pos - j >= a
+            D[left, 2 * j - 2] = vq[left] - vq[pos[left] - j]
+            right = pos + j < b
+            D[right, 2 * j - 1] = vq[pos[right] + j] - vq[right]
+        D.sort(axis=1)
+        r = D[pos, k_all[order][ranks] - 1]
+        radius = np.nextafter(r, 0.0)
+        rad2 = radius * radius
+        hi = _mi_reach(v, ranks, rad2, True)
+        lo = _mi_reach(v, ranks, rad2, False)
+        m_all[rows[order[ranks]], f] = (hi - lo + 1).astype(np.int32)
+        mi[f] = const - np.mean(psi[m_all[rows, f] - 1])    # mean in row order, as sklearn
+    return mi, m_all

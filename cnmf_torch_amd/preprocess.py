@@ -357,16 +357,34 @@ class Preprocess:
         return X_corr, X_pca_harmony
 
     def select_features_MI(self, _adata, cluster, max_scaled_thresh=None, quantile_thresh=.9999,
-                           n_top_features=70, makeplots=True):
-        """Mutual-information feature ranking against cluster labels (preprocess.py:391-439)."""
-        from sklearn.feature_selection import mutual_info_classif
+                           n_top_features=70, makeplots=True, backend="sklearn", device=None):
+        """Mutual-information feature ranking against cluster labels (preprocess.py:391-439).
 
+        ``backend="sklearn"`` (default) calls scikit-learn's ``mutual_info_classif``.
+        ``backend="native"`` computes the same estimator with ``models.mi.
+        mutual_info_classif_native`` on ``device`` (None: the GPU when one is visible;
+        mi_cd.hip there) without importing scikit-learn.  The two agree to 1e-12 when every
+        label has 2 or >= 8 cells; for labels of 3 to 7 cells scikit-learn's brute-force
+        neighbour search cancels at the noise scale and the native backend, which uses
+        exact differences, does not imitate it (docs/ARCHITECTURE.md "Mutual information")."""
+        if backend not in ("sklearn", "native"):
+            raise ValueError(f"select_features_MI: backend must be 'sklearn' or 'native', "
+                             f"not {backend!r}")
         ad = pp.normalize_total(to_lite(_adata))
         ad = stdscale_quantile_celing(ad, max_value=max_scaled_thresh,
                                       quantile_thresh=quantile_thresh)
         Xd = ad.X.toarray() if sp.issparse(ad.X) else ad.X
-        res = mutual_info_classif(Xd, cluster, discrete_features="auto", n_neighbors=3, copy=True,
-                                  random_state=self.random_seed)
+        if backend == "native":
+            from .models.mi import mutual_info_classif_native
+
+            dev = torch.device(device) if device is not None else _default_device()
+            res = mutual_info_classif_native(Xd, cluster, n_neighbors=3,
+                                             random_state=self.random_seed, device=dev)
+        else:
+            from sklearn.feature_selection import mutual_info_classif
+
+            res = mutual_info_classif(Xd, cluster, discrete_features="auto", n_neighbors=3,
+                                      copy=True, random_state=self.random_seed)
         res = pd.Series(res, index=ad.var.index).sort_values(ascending=False)
         resdf = pd.DataFrame([res.values, np.arange(res.shape[0])], columns=res.index,
                              index=["MI", "MI_Rank"]).T

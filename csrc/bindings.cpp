@@ -549,6 +549,18 @@ PYBIND11_MODULE(_hip, m) {
                           k, P<double>(out), ldo, reinterpret_cast<hipStream_t>(stream)),
           "seg_median");
   });
+  m.def("mi_cd_tile", []() { return cnmf_mi_cd_tile(); });
+  m.def("mi_cd", [](uintptr_t vals, uintptr_t perm, uintptr_t ranks, uintptr_t cid,
+                    uintptr_t seg, uintptr_t psi, int F, int n, int n_neighbors, uintptr_t part,
+                    int tiles, uintptr_t sum, uintptr_t m_out, long long ldm, uintptr_t rowmap,
+                    uintptr_t stream) {
+    check(cnmf_mi_cd(P<const double>(vals), P<const long long>(perm),
+                     P<const long long>(ranks), P<const int>(cid), P<const int>(seg),
+                     P<const double>(psi), F, n, n_neighbors, P<double>(part), tiles,
+                     P<double>(sum), P<int>(m_out), ldm, P<const int>(rowmap),
+                     reinterpret_cast<hipStream_t>(stream)),
+          "mi_cd");
+  });
   m.def("gemm_planes_bk", [](int pb) { return cnmf_gemm_planes_bk(pb); });
   m.def("gemm_planes_tile", [](int v, int which) { return cnmf_gemm_planes_tile(v, which); });
   m.def("gemm_planes",

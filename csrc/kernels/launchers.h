@@ -232,6 +232,14 @@ int cnmf_seg_median_max_rows();
 int cnmf_seg_median_max_clusters();
 hipError_t cnmf_seg_median(const double* S, long long lds, int n, int G, const int* perm,
                            const int* seg, int k, double* out, long long ldo, hipStream_t stream);
+// mi_cd.hip: Ross (2014) mutual information of F sorted continuous features against one
+// discrete target -- per point the k-th same-class neighbour radius and the count of all
+// points inside it (squared predicate), psi(count) summed per feature in a fixed order
+int cnmf_mi_cd_tile();
+hipError_t cnmf_mi_cd(const double* vals, const long long* perm, const long long* ranks,
+                      const int* cid, const int* seg, const double* psi, int F, int n,
+                      int n_neighbors, double* part, int tiles, double* sum, int* m_out,
+                      long long ldm, const int* rowmap, hipStream_t stream);
 int cnmf_gemm_planes_bk(int pb);
 int cnmf_gemm_planes_tile(int v, int which);
 hipError_t cnmf_gemm_planes(const unsigned short* A, long long lda, long long a_plane, int a_rows,
