@@ -2164,8 +2164,13 @@ def harmony_block_update(Rt: torch.Tensor, distT: torch.Tensor | None, sigma: to
     (nvar, N); E/O (K, B) float64.  ``distT`` (N, K) float64, or None: the distances
     2 (1 - Y_k . z_n) are formed inside the assign from ``Y`` (d, K) and ``Zt`` (N, d),
     and the assignment's objective terms (sum R dist, sum sigma R log R) are added to
-    ``obj`` (2,) float64.  ``ws`` caches the partial-sum workspace and the penalty table
-    (ws["pen"], which step 1 reads)."""
+    ``obj`` (2,) float64 (with ``distT`` no objective terms are formed and ``obj`` is not
+    touched).  sigma (K,), theta and Pr_b (B,) float64.  ``ws`` caches the partial-sum
+    workspace and the penalty table (ws["pen"] (K, B), which step 1 reads; one the caller
+    has set is kept).  A tensor of another dtype, shape, layout or device raises ValueError
+    before anything is launched."""
+    if Rt.dim() != 2 or E.dim() != 2 or bidx.dim() != 2:
+        raise ValueError("harmony_block_update: Rt (N, K), E (K, B) and bidx (nvar, N) required")
     N, K = Rt.shape
     B = E.shape[1]
     nvar = bidx.shape[0]
@@ -2175,18 +2180,28 @@ def harmony_block_update(Rt: torch.Tensor, distT: torch.Tensor | None, sigma: to
                         ("bidx", bidx, torch.int32)):
         if t.dtype != dt or not t.is_contiguous() or t.device != Rt.device:
             raise ValueError(f"{name}: contiguous {dt} on {Rt.device} required")
-    if O.shape != (K, B) or bidx.shape[1] != N:
+    if not Rt.is_cuda:
+        raise ValueError("harmony_block_update: tensors on the GPU required")
+    if tuple(E.shape) != (K, B) or tuple(O.shape) != (K, B) or bidx.shape[1] != N:
         raise ValueError("harmony_block_update: inconsistent shapes")
+    # (the kernels read these as raw float64 words and write K * B doubles into ws["pen"])
+    for name, t, shp in (("sigma", sigma, (K,)), ("theta", theta, (B,)), ("Pr_b", Pr_b, (B,)),
+                         ("ws['pen']", ws.get("pen"), (K, B))):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or
+                              tuple(t.shape) != shp or t.device != Rt.device):
+            raise ValueError(f"{name}: contiguous float64 {shp} on {Rt.device} required")
     d = 0
     if distT is None:
         if Y is None or Zt is None or obj is None:
             raise ValueError("harmony_block_update: Y, Zt and obj for the fused distances")
         d = int(Y.shape[0])
         for name, t, shp in (("Y", Y, (d, K)), ("Zt", Zt, (N, d)), ("obj", obj, (2,))):
-            if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shp:
-                raise ValueError(f"{name}: contiguous float64 {shp} required")
-    elif distT.dtype != torch.float64 or not distT.is_contiguous() or distT.shape != (N, K):
-        raise ValueError("distT: contiguous float64 (N, K) required")
+            if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shp or \
+                    t.device != Rt.device:
+                raise ValueError(f"{name}: contiguous float64 {shp} on {Rt.device} required")
+    elif distT.dtype != torch.float64 or not distT.is_contiguous() or \
+            tuple(distT.shape) != (N, K) or distT.device != Rt.device:
+        raise ValueError(f"distT: contiguous float64 (N, K) on {Rt.device} required")
     # ~512 workgroups of up to 4 waves (2 per CU): each wave walks a few dozen cells
     chunk = max(16, -(-nb // 512))
     n_wg = -(-nb // chunk)
@@ -2241,7 +2256,17 @@ def harmony_objective(O: torch.Tensor, E: torch.Tensor, sigma: torch.Tensor,
     """out[0] = obj[0] + obj[1] + sum_{k,b} sigma_k theta_b O log((O + 1) / (E + 1)) (the
     round's Harmony objective from the assign passes' sums and the cross-entropy term,
     which O = R Phi^T reduces to K x B numbers); resets obj."""
+    if O.dim() != 2:
+        raise ValueError("harmony_objective: O (K, B) required")
     K, B = O.shape
+    for name, t, shp in (("O", O, (K, B)), ("E", E, (K, B)), ("sigma", sigma, (K,)),
+                         ("theta", theta, (B,)), ("obj", obj, (2,)), ("out", out, None)):
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.device != O.device or \
+                (tuple(t.shape) != shp if shp is not None else t.dim() != 1 or t.numel() < 1):
+            raise ValueError(f"harmony_objective: {name} contiguous float64 "
+                             f"{shp if shp is not None else '(>= 1,)'} on {O.device} required")
+    if K < 1 or B < 1 or not O.is_cuda:
+        raise ValueError("harmony_objective: a non-empty (K, B) table on the GPU required")
     _hip.harmony_objective(O.data_ptr(), E.data_ptr(), sigma.data_ptr(), theta.data_ptr(), K, B,
                            obj.data_ptr(), out.data_ptr(), _stream_ptr(O))
 

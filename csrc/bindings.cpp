@@ -462,6 +462,8 @@ PYBIND11_MODULE(_hip, m) {
   });
 
   m.def("harmony_max_kb", []() { return cnmf_harmony_max_kb(); });
+  m.def("harmony_block_waves",
+        [](int K, int B, int d) { return cnmf_harmony_block_waves(K, B, d); });
   m.def("harmony_block", [](int op, uintptr_t Rt, uintptr_t distT, uintptr_t sigma,
                             uintptr_t cells, uintptr_t bidx, int nb, int N, int K, int B,
                             int nvar, int chunk, uintptr_t E, uintptr_t O, uintptr_t Pr_b,

@@ -216,8 +216,9 @@ __global__ void __launch_bounds__(4 * kHarmLanes) harmony_block_kernel(HarmonyPa
     if (k < K) ksum[wave * K + k] = s[j];
   }
   __syncthreads();
-  // the waves' sums in wave order -> this workgroup's partial row
-  if (ASSIGN) {
+  // the waves' sums in wave order -> this workgroup's partial row (sobj exists in the
+  // fused-distance layout only: an assign from distT reports no objective terms)
+  if (fused) {
     const double a = wave_sum(okm), b = wave_sum(oent);
     if (lane == 0) {
       sobj[2 * wave] = a;
@@ -228,7 +229,7 @@ __global__ void __launch_bounds__(4 * kHarmLanes) harmony_block_kernel(HarmonyPa
   double* mine = p.part + (long long)blockIdx.x * (K * (B + 1) + 2);
   if (threadIdx.x == 0) {
     double a = 0.0, b = 0.0;
-    if (ASSIGN)
+    if (fused)
       for (int w = 0; w < W; ++w) {
         a += sobj[2 * w];
         b += sobj[2 * w + 1];
@@ -407,6 +408,19 @@ __global__ void __launch_bounds__(256) harmony_objective_kernel(const double* __
 extern "C" int cnmf_harmony_max_kb() { return cnmf::kHarmMaxKB; }
 extern "C" int cnmf_harmony_centroid_max_d() { return cnmf::kHarmCenMaxD; }
 
+// Waves per workgroup of the block kernels for K clusters, B batch levels and d PCs in the
+// assign's LDS (d = 0: distances read from distT): the most (<= 4) whose O tables fit the
+// LDS budget beside the assign's tables -- both ops of a block update run the same count.
+// 0: no launch takes these sizes.
+extern "C" int cnmf_harmony_block_waves(int K, int B, int d) {
+  if (K < 1 || K > cnmf::kHarmLanes * cnmf::kHarmKPL || B < 1 ||
+      (long long)K * B > cnmf::kHarmMaxKB || d < 0 || d > cnmf::kHarmLanes)
+    return 0;
+  for (int w = 4; w >= 1; --w)
+    if (cnmf::harmony_lds_doubles(w, K, B, true, d) * 8 <= cnmf::kHarmLdsBytes) return w;
+  return 0;
+}
+
 // Y (d x K) = Zt^T Rt over N cells; part needs ceil(N / chunk) * d * K doubles
 extern "C" hipError_t cnmf_harmony_centroid(const double* Zt, const double* Rt, int N, int d,
                                             int K, int chunk, double* part, double* Y,
@@ -452,18 +466,14 @@ extern "C" hipError_t cnmf_harmony_block(int op, double* Rt, const double* distT
   if (nvar > cnmf::kHarmLanes) return hipErrorInvalidValue;
   if (op != 0 && !distT && (!Y || !Zt || d < 1 || d > cnmf::kHarmLanes))
     return hipErrorInvalidValue;
+  // (the objective terms go with the fused distances only)
   cnmf::HarmonyParams p{Rt, distT, sigma, cells, bidx, nb, N, K, B, nvar, chunk,
-                        E, O, Pr_b, theta, Pen, part, Y, Zt, distT ? 0 : d, obj};
+                        E, O, Pr_b, theta, Pen, part, Y, Zt, distT ? 0 : d,
+                        distT ? nullptr : obj};
   const int n_wg = (nb + chunk - 1) / chunk;
   const bool assign = op != 0;
-  int W = 1;
-  for (int w = 4; w >= 1; --w)
-    if (cnmf::harmony_lds_doubles(w, K, B, true, p.d) * 8 <= cnmf::kHarmLdsBytes) {
-      W = w;
-      break;
-    }
-  if (cnmf::harmony_lds_doubles(W, K, B, assign, p.d) * 8 > cnmf::kHarmLdsBytes)
-    return hipErrorInvalidValue;
+  const int W = cnmf_harmony_block_waves(K, B, p.d);
+  if (W < 1) return hipErrorInvalidValue;
   const size_t lds = (size_t)cnmf::harmony_lds_doubles(W, K, B, assign, p.d) * sizeof(double);
   static bool attr_done[2] = {false, false};
   const void* fn = assign ? reinterpret_cast<const void*>(&cnmf::harmony_block_kernel<true>)

@@ -149,6 +149,7 @@ hipError_t cnmf_seg_argmin(const double* D, long long ldd, int n, int nseg, int 
                            double* mind, hipStream_t stream);
 
 int cnmf_harmony_max_kb();
+int cnmf_harmony_block_waves(int K, int B, int d);
 hipError_t cnmf_harmony_block(int op, double* Rt, const double* distT, const double* sigma,
                               const int* cells, const int* bidx, int nb, int N, int K, int B,
                               int nvar, int chunk, double* E, double* O, const double* Pr_b,
