@@ -12,7 +12,8 @@ not a dependency here, so each is re-implemented with the same numerics:
   local quadratic (loess, span 0.3) fit of log10 variance on log10 mean; skmisc's
   loess is not installed, so a direct tricube-weighted local regression is used
   (``surface='direct'`` equivalent; parity with skmisc's interpolated surface is
-  within loess smoothing noise -- "parity unpinned").
+  within loess smoothing noise -- "parity unpinned").  ``loess="native"`` computes the
+  same fit in O(genes) memory through ``ops.loess`` (loess.hip on the GPU).
 * ``pca`` -- zero-centred truncated PCA via a (device) SVD, preprocess.py:310.
 """
 from __future__ import annotations
@@ -137,13 +138,38 @@ def filter_cells(adata, min_counts: float | None = None, min_genes: int | None =
 
 
 # ----------------------------------------------------------------------------- loess
+def _loess_device(device, device_csr=None) -> torch.device:
+    """Where the native fit runs: with the resident counts, else ``device``, else the GPU
+    when one is visible."""
+    if device_csr is not None:
+        return torch.device(device_csr.device)
+    if device is not None:
+        return torch.device(device)
+    from ..utils.gpu import visible
+
+    return torch.device("cuda") if visible() else torch.device("cpu")
+
+
 def loess_fit(x: np.ndarray, y: np.ndarray, span: float = 0.3, degree: int = 2,
-              device=None) -> np.ndarray:
+              device=None, backend: str = "direct") -> np.ndarray:
     """Direct local polynomial regression (tricube weights, nearest span*n points).
 
     Batched on the device: for each evaluation point the k nearest neighbours are
     found by sorting x once and sliding a window, then a weighted least-squares fit of
-    the given degree is solved for all points at once."""
+    the given degree is solved for all points at once.
+
+    ``backend="native"`` computes the same fit with ``ops.loess`` in O(n) memory on
+    ``device`` (None: the GPU when one is visible; loess.hip there, the float64 reference
+    on the CPU); ``"direct"`` (default) holds (n, k) windows."""
+    if backend not in ("direct", "native"):
+        raise ValueError(f"loess_fit: backend must be 'direct' or 'native', not {backend!r}")
+    if backend == "native":
+        from .. import ops
+
+        dev = _loess_device(device)
+        xt = torch.from_numpy(np.array(x, dtype=np.float64)).to(dev)
+        yt = torch.from_numpy(np.array(y, dtype=np.float64)).to(dev)
+        return ops.loess(xt, yt, span=span, degree=degree).cpu().numpy()
     n = x.shape[0]
     k = max(degree + 1, int(np.ceil(span * n)))
     k = min(k, n)
@@ -184,16 +210,56 @@ def loess_fit(x: np.ndarray, y: np.ndarray, span: float = 0.3, degree: int = 2,
     return out
 
 
+def _loess_ragged(stats, span: float, dev: torch.device) -> list:
+    """The fits of log10 variance on log10 mean over the genes of non-zero variance of every
+    batch in ``stats`` ((mean, var) per batch), as one ragged ``ops.loess`` call on ``dev``."""
+    from .. import ops
+
+    xs = [np.log10(mean[var > 0]) for mean, var in stats]
+    ys = [np.log10(var[var > 0]) for _, var in stats]
+    off = np.concatenate([[0], np.cumsum([x.shape[0] for x in xs])]).astype(np.int64)
+    fit = ops.loess(torch.from_numpy(np.concatenate(xs)).to(dev),
+                    torch.from_numpy(np.concatenate(ys)).to(dev), offsets=off,
+                    span=span).cpu().numpy()
+    return [fit[a:b] for a, b in zip(off[:-1], off[1:])]
+
+
+def _norm_var_resident(device_csr, m_t: torch.Tensor, v_t: torch.Tensor, span: float):
+    """Normalised variance of every gene of one batch held as a DeviceCSR, from its device
+    mean ``m_t`` and variance ``v_t``: the fit (``ops.loess``), the clip and the clipped
+    moments stay on the device; the result comes back as a numpy array."""
+    from .. import ops
+    from ..ops import sparse as sops
+
+    N = device_csr.shape[0]
+    not_const = v_t > 0
+    est = torch.zeros_like(m_t)
+    est[not_const] = ops.loess(torch.log10(m_t[not_const]), torch.log10(v_t[not_const]),
+                               span=span)
+    reg_std = torch.sqrt(10 ** est)
+    s1, sq, _ = sops.col_stats(device_csr, clip=reg_std * np.sqrt(N) + m_t)
+    nv = (1.0 / ((N - 1) * reg_std ** 2)) * (N * m_t ** 2 + sq - 2 * s1 * m_t)
+    return torch.nan_to_num(nv, nan=0.0).cpu().numpy()
+
+
 def highly_variable_genes(adata, flavor: str = "seurat_v3", n_top_genes: int = 2000,
                           batch_key: str | None = None, span: float = 0.3, inplace: bool = True,
-                          device_csr=None):
+                          device_csr=None, loess: str = "direct", device=None):
     """Seurat v3 HVG selection on raw counts (preprocess.py:295).
 
     ``device_csr``: the same counts already resident on the GPU as an
     :class:`ops.sparse.DeviceCSR` -- the per-gene mean/variance and the clipped second
-    moments are then column-statistics kernels over the stored entries (one batch)."""
+    moments are then column-statistics kernels over the stored entries (one batch).
+
+    ``loess``: ``"direct"`` (default) fits with :func:`loess_fit` as it stands, one call per
+    batch on the CPU.  ``"native"`` fits all batches in one ragged ``ops.loess`` call in O(n)
+    memory, on the device of ``device_csr`` when that is given (the means, variances and the
+    clip then stay there), else on ``device`` (None: the GPU when one is visible)."""
     if flavor != "seurat_v3":
         raise NotImplementedError("only flavor='seurat_v3' is used by Preprocess")
+    if loess not in ("direct", "native"):
+        raise ValueError(f"highly_variable_genes: loess must be 'direct' or 'native', "
+                         f"not {loess!r}")
     adata = to_lite(adata)
     X = adata.X
     batches = (pd.Series(np.zeros(adata.n_obs, dtype=int)) if batch_key is None
@@ -207,13 +273,29 @@ def highly_variable_genes(adata, flavor: str = "seurat_v3", n_top_genes: int = 2
         means_all, vars_all = m_t.cpu().numpy(), v_t.cpu().numpy()
     else:
         means_all, vars_all = _mean_var_ddof1(X)
-    for b in np.unique(batches.values):
+    batch_ids = np.unique(batches.values)
+    stats = fits = None
+    if loess == "native" and dev_stats:
+        # one batch on the resident counts: statistics, fit and clip stay on the device
+        norm_vars.append(_norm_var_resident(device_csr, m_t, v_t, span))
+        batch_ids = batch_ids[:0]
+    elif loess == "native":
+        stats = [_mean_var_ddof1(X[np.flatnonzero(batches.values == b)]) for b in batch_ids]
+        fits = _loess_ragged(stats, span, _loess_device(device, device_csr))
+    for bi, b in enumerate(batch_ids):
         rows = np.flatnonzero(batches.values == b)
         Xb = X if dev_stats else X[rows]
-        mean, var = (means_all, vars_all) if dev_stats else _mean_var_ddof1(Xb)
+        if stats is not None:
+            mean, var = stats[bi]
+        else:
+            mean, var = (means_all, vars_all) if dev_stats else _mean_var_ddof1(Xb)
         not_const = var > 0
         est = np.zeros(X.shape[1], dtype=np.float64)
-        est[not_const] = loess_fit(np.log10(mean[not_const]), np.log10(var[not_const]), span=span)
+        if fits is not None:
+            est[not_const] = fits[bi]
+        else:
+            est[not_const] = loess_fit(np.log10(mean[not_const]), np.log10(var[not_const]),
+                                       span=span)
         reg_std = np.sqrt(10 ** est)
         N = Xb.shape[0]
         clip = reg_std * np.sqrt(N) + mean

@@ -2024,6 +2024,84 @@ def mi_cd(Xp: torch.Tensor, codes, n_neighbors: int = 3, return_counts: bool = F
     return (mi, m_out) if return_counts else mi
 
 
+def loess(x: torch.Tensor, y: torch.Tensor, offsets=None, span: float = 0.3, degree: int = 2,
+          return_windows: bool = False, timings: dict | None = None):
+    """Local polynomial regression (tricube weights, the nearest ``span`` share of the points,
+    degree 1 or 2) of the float64 tensor ``y`` on ``x`` at the points themselves: the fitted
+    values in input order, on x's device.  ``offsets`` (host integers, B + 1 bounds) marks B
+    independent, possibly empty series inside x / y; None is one series.  ``return_windows``
+    also returns the window start of every sorted point inside its series (int64) and the
+    sort order (int64 indices into x, series by series).  The contract is
+    :func:`reference.loess`, which is also the CPU path.
+
+    GPU (loess.hip): a stable ``torch.sort`` (for several series a second stable sort by
+    series puts every series back in its place), one thread per point for the window start,
+    one wave per point for the moments and the solve, then an index scatter.  The state is
+    O(n); the sums are formed in a fixed order, so every run gives the same bits.
+    ``timings``: a dict that receives the synchronised ``sort``, ``windows`` and ``fit``
+    seconds (benchmarks only)."""
+    if int(degree) != degree or int(degree) not in (1, 2):
+        raise ValueError("loess: degree must be 1 or 2")
+    degree = int(degree)
+    if not float(span) > 0:
+        raise ValueError("loess: span must be positive")
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 1:
+            raise ValueError(f"loess: {name} must be a 1-D float64 tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"loess: {name} must be contiguous")
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError("loess: x and y must have the same length and device")
+    n = int(x.shape[0])
+    if n >= (1 << 31):
+        raise ValueError("loess: fewer than 2^31 points are required")
+    off = reference.loess_offsets(offsets, n)
+    if not (bool(torch.isfinite(x).all()) and bool(torch.isfinite(y).all())):
+        raise ValueError("loess: non-finite input")
+    dev = x.device
+    if not use_native(x):
+        fit, starts, order = reference.loess(x.cpu().numpy(), y.cpu().numpy(), off, span,
+                                             degree, return_windows=True)
+        out = torch.from_numpy(fit).to(dev)
+        return ((out, torch.from_numpy(starts).to(dev), torch.from_numpy(order).to(dev))
+                if return_windows else out)
+    B = off.shape[0] - 1
+    lens = np.diff(off)
+    ks = np.array([reference.loess_k(int(m), span, degree) for m in lens], dtype=np.int32)
+    off_t = torch.from_numpy(off.astype(np.int32)).to(dev)
+    ks_t = torch.from_numpy(ks).to(dev)
+
+    def lap():      # a synchronised clock, only when the caller asked for timings
+        if timings is None:
+            return 0.0
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    t0 = lap()
+    xs, order = torch.sort(x, stable=True)
+    if B > 1:
+        sid = torch.repeat_interleave(torch.arange(B, device=dev),
+                                      torch.from_numpy(lens).to(dev), output_size=n)
+        order = order[torch.sort(sid[order], stable=True).indices]
+        xs = x[order]
+    ys = y[order]
+    starts = torch.empty(n, dtype=torch.int32, device=dev)
+    fit_sorted = torch.empty(n, dtype=torch.float64, device=dev)
+    stream = _stream_ptr(x)
+    t1 = lap()
+    _hip.loess_windows(xs.data_ptr(), off_t.data_ptr(), ks_t.data_ptr(), B, n,
+                       starts.data_ptr(), stream)
+    t2 = lap()
+    _hip.loess_fit(xs.data_ptr(), ys.data_ptr(), off_t.data_ptr(), ks_t.data_ptr(),
+                   starts.data_ptr(), B, n, degree, fit_sorted.data_ptr(), stream)
+    t3 = lap()
+    if timings is not None:
+        timings.update(sort=t1 - t0, windows=t2 - t1, fit=t3 - t2)
+    out = torch.empty_like(x)
+    out[order] = fit_sorted
+    return (out, starts.to(torch.int64), order) if return_windows else out
+
+
 def kmeanspp_fused_ok(X: torch.Tensor, M: int) -> bool:
     """True when the fused k-means++ step (kmeans.hip kmeanspp_kernel) handles X (n, d) with
     M = n_init * trials candidates in LDS."""

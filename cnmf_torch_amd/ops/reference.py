@@ -664,3 +664,157 @@ def mi_cd(Xp, codes, n_neighbors: int = 3):
         m_all[rows[order[ranks]], f] = (hi - lo + 1).astype(np.int32)
         mi[f] = const - np.mean(psi[m_all[rows, f] - 1])    # mean in row order, as sklearn
     return mi, m_all
+
+
+# ---------------------------------------------------------------------------------------
+# LOESS: local polynomial regression with tricube weights over the k nearest points, the
+# direct fit of models/pp.py ``loess_fit`` in O(block * k) memory (docs/ARCHITECTURE.md
+# "LOESS").  CPU implementation and oracle of loess.hip.
+
+LOESS_BLOCK = 256
+LOESS_RIDGE = 1e-10
+LOESS_H_FACTOR = 1.0000001
+
+
+def loess_k(n: int, span: float, degree: int) -> int:
+    """Window size of a series of n points: min(n, max(degree + 1, ceil(span * n)))."""
+    return int(min(n, max(degree + 1, int(np.ceil(span * n)))))
+
+
+def loess_offsets(offsets, n: int) -> np.ndarray:
+    """``offsets`` as a validated int64 array of B + 1 series bounds over n points (None: one
+    series): starts at 0, never decreases, ends at n."""
+    if offsets is None:
+        return np.array([0, int(n)], dtype=np.int64)
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.cpu().numpy()
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.size < 2 or off.dtype.kind not in "iu":
+        raise ValueError("loess: offsets must be a 1-D integer array of B + 1 bounds")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != int(n) or (np.diff(off) < 0).any():
+        raise ValueError("loess: offsets must start at 0, never decrease and end at len(x)")
+    return off
+
+
+def loess_windows(xs, k: int) -> np.ndarray:
+    """Window starts (int64) of the sorted float64 series ``xs`` for windows of k points:
+    start_i is the first lo in [0, n - k] at which ``xs[lo + k] - xs[i] < xs[i] - xs[lo]`` is
+    false (lo = n - k counts as false).  The predicate is monotone in lo, so a bisection per
+    point, with no state carried between points, finds it; its first-false point does not
+    decrease with i, so this is where the sliding loop of ``pp.loess_fit`` stops."""
+    xs = np.asarray(xs, dtype=np.float64)
+    n, k = xs.shape[0], int(k)
+    if n == 0:
+        return np.zeros(0, dtype=np.int64)
+    if not 1 <= k <= n:
+        raise ValueError("loess_windows: k must be in 1..len(xs)")
+    lo = np.zeros(n, dtype=np.int64)
+    hi = np.full(n, n - k, dtype=np.int64)
+    while True:
+        open_ = lo < hi
+        if not open_.any():
+            return lo
+        mid = (lo + hi) // 2                         # < n - k wherever open
+        step = open_ & ((xs[np.minimum(mid + k, n - 1)] - xs) < (xs - xs[mid]))
+        lo = np.where(step, mid + 1, lo)
+        hi = np.where(open_ & ~step, mid, hi)
+
+
+def _loess_solve0(S, T):
+    """First component of (S_{a+b} + ridge I)^-1 T for every row: Gaussian elimination with
+    partial pivoting (the first row of the largest magnitude), elementwise over the rows."""
+    m = len(T)
+    A = np.empty((S[0].shape[0], m, m + 1), dtype=np.float64)
+    for a in range(m):
+        for c in range(m):
+            A[:, a, c] = S[a + c] + (LOESS_RIDGE if a == c else 0.0)
+        A[:, a, m] = T[a]
+    for c in range(m):
+        for r in range(c + 1, m):
+            swap = np.abs(A[:, r, c]) > np.abs(A[:, c, c])
+            A[swap, c], A[swap, r] = A[swap, r], A[swap, c]
+        for r in range(c + 1, m):
+            f = A[:, r, c] / A[:, c, c]
+            A[:, r, c:] -= f[:, None] * A[:, c, c:]
+    coef = [None] * m
+    for a in range(m - 1, -1, -1):
+        v = A[:, a, m].copy()
+        for c in range(a + 1, m):
+            v -= A[:, a, c] * coef[c]
+        coef[a] = v / A[:, a, a]
+    return coef[0]
+
+
+def _loess_sorted(xs, ys, k: int, starts, degree: int, block: int, points=None) -> np.ndarray:
+    """Fitted values of the sorted series at its own points (or at the sorted positions
+    ``points`` only), ``block`` points at a time."""
+    pts = np.arange(xs.shape[0]) if points is None else np.asarray(points, dtype=np.int64)
+    out = np.empty(pts.shape[0], dtype=np.float64)
+    win = np.arange(k)
+    for a in range(0, pts.shape[0], block):
+        i = pts[a:a + block]
+        s = starts[i]
+        idx = s[:, None] + win[None, :]
+        xi = xs[i]
+        d = xs[idx] - xi[:, None]
+        yw = ys[idx]
+        h = np.maximum(xi - xs[s], xs[s + k - 1] - xi)      # = |d|.max(): the window is sorted
+        h = np.where(h > 0, h * LOESS_H_FACTOR, 1.0)
+        r = np.abs(d) / h[:, None]
+        u = np.maximum(1.0 - r * r * r, 0.0)
+        pw = u * u * u                                       # w d^p
+        S, T = [], []
+        for p in range(2 * degree + 1):
+            S.append(pw.sum(axis=1))
+            if p <= degree:
+                T.append((pw * yw).sum(axis=1))
+            pw = pw * d
+        out[a:a + i.shape[0]] = _loess_solve0(S, T)
+    return out
+
+
+def loess(x, y, offsets=None, span: float = 0.3, degree: int = 2, block: int = LOESS_BLOCK,
+          return_windows: bool = False):
+    """Fitted values (float64, input order) of the local regression of y on x at the points
+    themselves, for B independent series laid end to end: series b is
+    ``[offsets[b], offsets[b + 1])`` (ragged, possibly empty; None: one series).
+
+    Per series of n points: stable sort by x, k = ``loess_k(n, span, degree)``, window starts
+    by :func:`loess_windows`.  Per point i with d = x_window - x_i: h = the larger distance to
+    the two window ends, times 1.0000001, or 1 when it is 0; w = max(1 - (|d| / h)^3, 0)^3;
+    S_p = sum w d^p (p <= 2 degree), T_p = sum w d^p y (p <= degree), the powers formed by
+    multiplication; the fitted value is the first component of (S_{a+b} + 1e-10 I)^-1 T by
+    Gaussian elimination with partial pivoting.  ``block`` points are in flight at a time
+    (memory O(block * k)); every row is reduced on its own, so the result does not depend on
+    ``block``.  ``return_windows``: also the window starts (int64, inside each series, sorted
+    order) and the sort order (int64 indices into x, series by series)."""
+    degree = int(degree)
+    if degree not in (1, 2):
+        raise ValueError("loess: degree must be 1 or 2")
+    if not float(span) > 0:
+        raise ValueError("loess: span must be positive")
+    if int(block) < 1:
+        raise ValueError("loess: block must be positive")
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    if x.shape != y.shape:
+        raise ValueError("loess: x and y must have the same length")
+    off = loess_offsets(offsets, x.shape[0])
+    if not (np.isfinite(x).all() and np.isfinite(y).all()):
+        raise ValueError("loess: non-finite input")
+    fitted = np.empty(x.shape[0], dtype=np.float64)
+    starts_all = np.zeros(x.shape[0], dtype=np.int64)
+    order_all = np.zeros(x.shape[0], dtype=np.int64)
+    for a, b in zip(off[:-1], off[1:]):
+        if b == a:
+            continue
+        order = np.argsort(x[a:b], kind="stable")
+        xs, ys = x[a:b][order], y[a:b][order]
+        k = loess_k(b - a, span, degree)
+        starts = loess_windows(xs, k)
+        fit = _loess_sorted(xs, ys, k, starts, degree, int(block))
+        fitted[a + order] = fit
+        starts_all[a:b] = starts
+        order_all[a:b] = a + order
+    return (fitted, starts_all, order_all) if return_windows else fitted

@@ -47,6 +47,11 @@ def _default_device():
     return torch.device("cuda") if visible() else torch.device("cpu")
 
 
+def _check_hvg_loess(hvg_loess):
+    if hvg_loess not in ("direct", "native"):
+        raise ValueError(f"hvg_loess must be 'direct' or 'native', not {hvg_loess!r}")
+
+
 def stdscale_quantile_celing(_adata, max_value=None, quantile_thresh=None):
     """Scale genes to unit variance (no centring), cap at ``max_value`` and at the
     global ``quantile_thresh`` quantile (preprocess.py:21-29).  The quantile is taken
@@ -139,9 +144,12 @@ class Preprocess:
                             adt_feature_name="Antibody Capture", harmony_vars=None,
                             n_top_rna_genes=2000, librarysize_targetsum=1e4,
                             max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
-                            theta=1, save_output_base=None, max_iter_harmony=20, device=None):
+                            theta=1, save_output_base=None, max_iter_harmony=20, device=None,
+                            hvg_loess="direct"):
         """HVG-filtered, normalised, optionally Harmony-corrected input for cNMF plus a
-        TP10K matrix (RNA [+ ADT]) for the tpm input (preprocess.py:135-247)."""
+        TP10K matrix (RNA [+ ADT]) for the tpm input (preprocess.py:135-247).
+        ``hvg_loess``: see :meth:`normalize_batchcorrect`."""
+        _check_hvg_loess(hvg_loess)
         if (not isinstance(_adata, Collection) or _is_anndata(_adata)) and feature_type_col is not None:
             ad = to_lite(_adata)
             is_adt = (ad.var[feature_type_col] == adt_feature_name).values
@@ -190,7 +198,8 @@ class Preprocess:
                 adata_RNA, harmony_vars=harmony_vars, n_top_genes=n_top_rna_genes,
                 librarysize_targetsum=librarysize_targetsum, max_scaled_thresh=max_scaled_thresh,
                 quantile_thresh=quantile_thresh, theta=theta, makeplots=makeplots,
-                max_iter_harmony=max_iter_harmony, device=dev, _device_csr=dX)
+                max_iter_harmony=max_iter_harmony, device=dev, _device_csr=dX,
+                hvg_loess=hvg_loess)
         except BaseException:
             if tp_write is not None:
                 tp_write.exception()    # no write left running behind the error
@@ -218,11 +227,17 @@ class Preprocess:
                                n_top_genes=None, librarysize_targetsum=1e4,
                                max_scaled_thresh=None, quantile_thresh=.9999, theta=1,
                                makeplots=True, max_iter_harmony=20, device=None,
-                               _device_csr=None):
+                               _device_csr=None, hvg_loess="direct"):
         """Seurat-v3 HVGs, scaling + quantile ceiling, optional Harmony (preprocess.py:250-338).
 
         On a GPU with sparse counts and ``harmony_vars``, the counts are uploaded once and
-        every step runs on the device (:meth:`_harmony_device`)."""
+        every step runs on the device (:meth:`_harmony_device`).
+
+        ``hvg_loess="direct"`` (default) fits the HVG mean-variance trend with
+        ``pp.loess_fit`` as before, on the CPU with (genes x window) temporaries;
+        ``"native"`` fits it with ``ops.loess`` in O(genes) memory on ``device``
+        (loess.hip on the GPU; docs/ARCHITECTURE.md "LOESS")."""
+        _check_hvg_loess(hvg_loess)
         ad = to_lite(_adata)
         dev = torch.device(device) if device is not None else _default_device()
         dX = _device_csr
@@ -230,7 +245,7 @@ class Preprocess:
             dX = _device_counts(ad, dev)
         if n_top_genes is not None:
             pp.highly_variable_genes(ad, flavor="seurat_v3", n_top_genes=n_top_genes,
-                                     device_csr=dX)
+                                     device_csr=dX, loess=hvg_loess, device=dev)
         elif "highly_variable" not in ad.var.columns:
             raise Exception("If a numeric value for n_top_genes is not provided, you must include "
                             "a highly_variable column in _adata")

@@ -563,6 +563,20 @@ PYBIND11_MODULE(_hip, m) {
                      reinterpret_cast<hipStream_t>(stream)),
           "mi_cd");
   });
+  m.def("loess_windows", [](uintptr_t xs, uintptr_t offsets, uintptr_t ks, int B, int n,
+                            uintptr_t starts, uintptr_t stream) {
+    check(cnmf_loess_windows(P<const double>(xs), P<const int>(offsets), P<const int>(ks), B, n,
+                             P<int>(starts), reinterpret_cast<hipStream_t>(stream)),
+          "loess_windows");
+  });
+  m.def("loess_fit", [](uintptr_t xs, uintptr_t ys, uintptr_t offsets, uintptr_t ks,
+                        uintptr_t starts, int B, int n, int degree, uintptr_t fitted,
+                        uintptr_t stream) {
+    check(cnmf_loess_fit(P<const double>(xs), P<const double>(ys), P<const int>(offsets),
+                         P<const int>(ks), P<const int>(starts), B, n, degree,
+                         P<double>(fitted), reinterpret_cast<hipStream_t>(stream)),
+          "loess_fit");
+  });
   m.def("gemm_planes_bk", [](int pb) { return cnmf_gemm_planes_bk(pb); });
   m.def("gemm_planes_tile", [](int v, int which) { return cnmf_gemm_planes_tile(v, which); });
   m.def("gemm_planes",

@@ -241,6 +241,15 @@ hipError_t cnmf_mi_cd(const double* vals, const long long* perm, const long long
                       const int* cid, const int* seg, const double* psi, int F, int n,
                       int n_neighbors, double* part, int tiles, double* sum, int* m_out,
                       long long ldm, const int* rowmap, hipStream_t stream);
+// loess.hip: local polynomial regression (tricube weights, the k nearest points as a
+// contiguous window of the sorted series) of B ragged series laid end to end -- the window
+// start of every point by binary search, then one wave per point for the weighted moments
+// and the (degree + 1)-square solve
+hipError_t cnmf_loess_windows(const double* xs, const int* offsets, const int* ks, int B, int n,
+                              int* starts, hipStream_t stream);
+hipError_t cnmf_loess_fit(const double* xs, const double* ys, const int* offsets,
+                          const int* ks, const int* starts, int B, int n, int degree,
+                          double* fitted, hipStream_t stream);
 int cnmf_gemm_planes_bk(int pb);
 int cnmf_gemm_planes_tile(int v, int which);
 hipError_t cnmf_gemm_planes(const unsigned short* A, long long lda, long long a_plane, int a_rows,
