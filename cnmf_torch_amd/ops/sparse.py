@@ -200,6 +200,9 @@ def col_stats(A: DeviceCSR, *, row_scale=None, col_map=None, n_out: int | None =
         return s, q, k
     _require_native()
     n = A.shape[0]
+    if n == 0 or n_out == 0:     # the launcher returns before launching: nothing fills the partials
+        z = torch.zeros((3, n_out), dtype=torch.float64, device=dev)
+        return z[0], z[1], z[2]
     nb = int(_hip.csr_stats_blocks(n))
     part = torch.empty((3, nb, n_out), dtype=torch.float64, device=dev)
     _hip.csr_col_stats(A.indptr.data_ptr(), A.indices.data_ptr(), A.data.data_ptr(),
@@ -326,6 +329,8 @@ def tspmm(A: DeviceCSR, B: torch.Tensor) -> torch.Tensor:
     if Bd.dtype not in (torch.float32, torch.float64):
         Bd = Bd.double()
     Bd = Bd.contiguous()
+    if A.shape[0] == 0 or n_out == 0:   # no launch (see col_stats): exact zeros
+        return torch.zeros((n_out, K), dtype=torch.float64, device=A.device)
     nb = int(_hip.csr_tspmm_blocks(A.shape[0]))
     part = torch.empty((nb, n_out, K), dtype=torch.float64, device=A.device)
     _hip.csr_tspmm(A.indptr.data_ptr(), A.indices.data_ptr(), A.data.data_ptr(),
@@ -338,7 +343,7 @@ def tspmm(A: DeviceCSR, B: torch.Tensor) -> torch.Tensor:
 def kth_nonneg(x: torch.Tensor, k: int) -> float:
     """The k-th smallest (0-based) of the non-negative entries of the float32 tensor x
     (negative entries are ignored), exactly: a 4-pass radix select over the IEEE bit
-    patterns (non-negative floats order like their uint32 images)."""
+    patterns (non-negative floats order like their uint32 images; a stored -0.0 is a zero)."""
     x = x.reshape(-1)
     if x.dtype != torch.float32:
         raise TypeError("kth_nonneg: float32 input expected")
@@ -346,7 +351,7 @@ def kth_nonneg(x: torch.Tensor, k: int) -> float:
         v = x[x >= 0]
         if not 0 <= k < v.numel():
             raise IndexError("kth_nonneg: k out of range")
-        return float(torch.kthvalue(v, k + 1).values)
+        return float(torch.kthvalue(v, k + 1).values) + 0.0    # -0.0 -> 0.0, as the kernel keys it
     _require_native()
     hist = torch.zeros(256, dtype=torch.int64, device=x.device)
     prefix, mask, need = 0, 0, int(k)

@@ -22,7 +22,8 @@
 //  * csr_transform     the transformed value of every stored entry (dropped -> -1).
 //  * csr_densify       transformed rows scattered into a zeroed dense (n x n_out) matrix.
 //  * radix_hist        one pass of an exact radix select over the float32 bit patterns
-//                      of non-negative values (negative values are skipped): 256-bin
+//                      of non-negative values (negative values are skipped, a zero of
+//                      either sign has the pattern 0): 256-bin
 //                      histogram of the byte at `shift` among values matching `prefix`;
 //                      LDS histograms flushed with integer atomics (exact).
 #include <hip/hip_runtime.h>
@@ -185,7 +186,7 @@ __global__ void __launch_bounds__(256) radix_hist_kernel(const float* __restrict
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
     const float v = x[i];
     if (!(v >= 0.0f)) continue;               // dropped entries (and NaN) are skipped
-    const unsigned int b = __float_as_uint(v);
+    const unsigned int b = v == 0.0f ? 0u : __float_as_uint(v);   // -0.0 is a zero, not 2^31
     if ((b & mask) == prefix) atomicAdd(&h[(b >> shift) & 255u], 1u);
   }
   __syncthreads();
