@@ -14,7 +14,8 @@ not a dependency here, so each is re-implemented with the same numerics:
   (``surface='direct'`` equivalent; parity with skmisc's interpolated surface is
   within loess smoothing noise -- "parity unpinned").  ``loess="native"`` computes the
   same fit in O(genes) memory through ``ops.loess`` (loess.hip on the GPU).
-* ``pca`` -- zero-centred truncated PCA via a (device) SVD, preprocess.py:310.
+* ``pca`` -- zero-centred truncated PCA from the (genes x genes) covariance, preprocess.py:310;
+  ``backend="csr"`` / ``pca_csr`` compute it from a device CSR without a dense copy.
 """
 from __future__ import annotations
 
@@ -335,18 +336,36 @@ def highly_variable_genes(adata, flavor: str = "seurat_v3", n_top_genes: int = 2
 
 
 def pca(adata, n_comps: int = 50, zero_center: bool = True, use_highly_variable: bool = False,
-        device=None, random_state: int = 0):
-    """Zero-centred PCA -> obsm['X_pca'], varm['PCs'], uns['pca'] (preprocess.py:310)."""
+        device=None, random_state: int = 0, backend: str = "dense"):
+    """Zero-centred PCA -> obsm['X_pca'], varm['PCs'], uns['pca'] (preprocess.py:310).
+
+    ``backend="dense"`` (default) densifies ``X`` into a float64 tensor on ``device``;
+    ``"csr"`` keeps a sparse ``X`` as a CSR on ``device`` (the HVG subset a col_map) and
+    factorises it with :func:`pca_csr` -- no dense copy anywhere."""
+    if backend not in ("dense", "csr"):
+        raise ValueError(f"pca: backend must be 'dense' or 'csr', not {backend!r}")
     adata = to_lite(adata)
     X = adata.X
     cols = np.arange(adata.n_vars)
     if use_highly_variable and "highly_variable" in adata.var:
         cols = np.flatnonzero(adata.var["highly_variable"].values)
-    Xs = X[:, cols]
-    Xd = Xs.toarray() if sp.issparse(Xs) else np.asarray(Xs)
     dev = torch.device(device) if device is not None else torch.device("cpu")
-    T = torch.as_tensor(Xd, dtype=torch.float64, device=dev)
-    Xp, Vh, var, ratio = pca_tensor(T, n_comps, zero_center)
+    if backend == "csr":
+        if not sp.issparse(X):
+            raise ValueError("pca: backend='csr' needs a sparse X")
+        from ..ops import sparse as sops
+
+        A = sops.DeviceCSR.from_scipy(X, device=dev)
+        if cols.size != adata.n_vars:
+            cmap = np.full(adata.n_vars, -1, np.int32)
+            cmap[cols] = np.arange(cols.size, dtype=np.int32)
+            A = A.view(col_map=cmap, n_out=int(cols.size))
+        Xp, Vh, var, ratio = pca_csr(A, n_comps, zero_center)
+    else:
+        Xs = X[:, cols]
+        Xd = Xs.toarray() if sp.issparse(Xs) else np.asarray(Xs)
+        T = torch.as_tensor(Xd, dtype=torch.float64, device=dev)
+        Xp, Vh, var, ratio = pca_tensor(T, n_comps, zero_center)
     adata.obsm["X_pca"] = Xp
     PCs = np.zeros((adata.n_vars, Vh.shape[0]))
     PCs[cols] = Vh.T
@@ -355,26 +374,60 @@ def pca(adata, n_comps: int = 50, zero_center: bool = True, use_highly_variable:
     return adata
 
 
-def pca_tensor(T: torch.Tensor, n_comps: int = 50, zero_center: bool = True):
-    """Zero-centred PCA of a (cells x features) tensor on its device (float64):
-    returns numpy (scores (n, c), components (c, features), variance, variance_ratio)."""
-    T = T.to(torch.float64)
-    dev = T.device
-    if zero_center:
-        T = T - T.mean(dim=0, keepdim=True)
-    n_comps = min(n_comps, min(T.shape) - 1) if min(T.shape) > 1 else 1
-    # top components from the (genes x genes) Gram matrix: one GEMM + a small eigh instead
-    # of a thin SVD of the whole (cells x genes) matrix (3.5 s -> ~0.1 s at 100k x 2k)
-    C = T.t() @ T
+def _clamp_comps(n_comps: int, shape) -> int:
+    return min(n_comps, min(shape) - 1) if min(shape) > 1 else 1
+
+
+def _pca_from_cov(C: torch.Tensor, n: int, n_comps: int, scores, total):
+    """The tail pca_tensor and pca_csr share: top ``n_comps`` eigenpairs of the (features x
+    features) matrix ``C`` = T^T T of the centred data, ``scores(Vh)`` = T @ Vh^T, the sign
+    rule and the variances (``total()`` = sum of squares of T).  Returns numpy (scores,
+    components, variance, variance_ratio)."""
+    dev = C.device
     evals, evecs = torch.linalg.eigh(C)
     order = torch.argsort(evals, descending=True)[:n_comps]
     S = torch.sqrt(torch.clamp(evals[order], min=0.0))
     Vh = evecs[:, order].t()
-    XS = T @ Vh.t()                                     # = U * S
+    XS = scores(Vh)                                     # = U * S
     # deterministic sign: largest |score| positive (sklearn svd_flip u-based)
     sign = torch.sign(XS[torch.argmax(torch.abs(XS), dim=0), torch.arange(XS.shape[1], device=dev)])
     sign[sign == 0] = 1
     XS, Vh = XS * sign, Vh * sign[:, None]
-    var = (S ** 2 / max(T.shape[0] - 1, 1)).cpu().numpy()
-    total = float((T ** 2).sum().cpu()) / max(T.shape[0] - 1, 1)
+    var = (S ** 2 / max(n - 1, 1)).cpu().numpy()
+    total = total() / max(n - 1, 1)
     return XS.cpu().numpy(), Vh.cpu().numpy(), var, (var / total if total > 0 else var)
+
+
+def pca_tensor(T: torch.Tensor, n_comps: int = 50, zero_center: bool = True):
+    """Zero-centred PCA of a (cells x features) tensor on its device (float64):
+    returns numpy (scores (n, c), components (c, features), variance, variance_ratio)."""
+    T = T.to(torch.float64)
+    if zero_center:
+        T = T - T.mean(dim=0, keepdim=True)
+    n_comps = _clamp_comps(n_comps, T.shape)
+    # top components from the (genes x genes) Gram matrix: one GEMM + a small eigh instead
+    # of a thin SVD of the whole (cells x genes) matrix (3.5 s -> ~0.1 s at 100k x 2k)
+    C = T.t() @ T
+    return _pca_from_cov(C, T.shape[0], n_comps, lambda Vh: T @ Vh.t(),
+                         lambda: float((T ** 2).sum().cpu()))
+
+
+def pca_csr(A, n_comps: int = 50, zero_center: bool = True, value_dtype=torch.float64):
+    """:func:`pca_tensor` of the matrix a :class:`ops.sparse.DeviceCSR` view stands for
+    (``densify(A, out_dtype=value_dtype)``) without building it: the covariance
+    T^T T - n mu mu^T from ``ops.sparse.gram`` and the column sums, the scores
+    T V - mu V from ``ops.sparse.project`` (pca_csr.hip on the GPU; docs/ARCHITECTURE.md
+    "Sparse PCA").  Same return value, sign rule and ``n_comps`` clamp."""
+    from ..ops import sparse as sops
+
+    n = A.shape[0]
+    B = sops.valued(A, value_dtype)          # the transform applied once, O(nnz)
+    C = sops.gram(B)
+    mu = None
+    if zero_center:
+        mu = sops.col_stats(B)[0] / n
+        C = C - n * torch.outer(mu, mu)
+    return _pca_from_cov(
+        C, n, _clamp_comps(n_comps, A.shape),
+        lambda Vh: sops.project(B, Vh.t(), None if mu is None else Vh @ mu),
+        lambda: float(torch.trace(C).cpu()))

@@ -340,6 +340,169 @@ def tspmm(A: DeviceCSR, B: torch.Tensor) -> torch.Tensor:
     return part.sum(dim=0)
 
 
+# ------------------------------------------------------------------------- sparse PCA
+_GRAM_TILE = 64          # kGrTile of csr_gram: output columns per tile
+
+
+def _value_dtype(value_dtype):
+    if value_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"value_dtype must be torch.float32 or torch.float64, not {value_dtype}")
+    return value_dtype
+
+
+def _check_injective(A: DeviceCSR, cm, n_out: int, op: str) -> None:
+    """The PCA kernels rely on distinct output columns within a row: a col_map that sends
+    two stored columns to one output column (or past the last one) is an error."""
+    if cm is None:
+        if A.n_stored_cols != n_out:
+            raise ValueError(f"{op}: the view has {n_out} columns, the stored matrix "
+                             f"{A.n_stored_cols}, and no col_map relates them")
+        return
+    if cm.numel() != A.n_stored_cols:
+        raise ValueError(f"{op}: col_map has {cm.numel()} entries, the stored matrix "
+                         f"{A.n_stored_cols} columns")
+    kept = cm[cm >= 0]
+    if kept.numel() == 0:
+        return
+    if int(kept.max()) >= n_out:
+        raise ValueError(f"{op}: col_map names output column {int(kept.max())}, "
+                         f"the view has {n_out}")
+    if int(torch.unique(kept).numel()) != int(kept.numel()):
+        raise ValueError(f"{op}: col_map sends two stored columns to one output column")
+
+
+def valued(A: DeviceCSR, value_dtype=torch.float64) -> DeviceCSR:
+    """``A`` with its transform applied to the stored values once (rounded to
+    ``value_dtype``, the value ``densify(out_dtype=value_dtype)`` would hold) and only the
+    col_map left in the view: what ``gram``, ``project`` and the column sums of a PCA all
+    read.  O(nnz) memory; ``A`` itself when it already is of that form."""
+    vd = _value_dtype(value_dtype)
+    x = A.xf
+    mv = x.get("max_value")
+    plain = (x.get("row_scale") is None and x.get("col_div") is None and x.get("clip") is None
+             and (mv is None or mv == float("inf")))
+    if plain and not (vd == torch.float32 and A.data.dtype == torch.float64):
+        return A
+    vals = transform(A, out_dtype=vd)
+    B = DeviceCSR(A.indptr, A.indices, vals, (A.shape[0], A.n_stored_cols),
+                  {"col_map": x.get("col_map")})
+    B.shape = A.shape
+    return B
+
+
+def _row_blocks(B: DeviceCSR, cm, rows_per_block: int):
+    """(r0, r1, dense float64 block) over the rows of a ``valued`` matrix: the CPU paths'
+    bounded-memory stand-in for the kernels' walk over the stored entries."""
+    n, nh = B.shape
+    for r0 in range(0, n, rows_per_block):
+        r1 = min(n, r0 + rows_per_block)
+        a, b = int(B.indptr[r0]), int(B.indptr[r1])
+        c = B.indices[a:b].long()
+        if cm is not None:
+            c = cm.long()[c]
+        keep = c >= 0
+        rows = torch.repeat_interleave(torch.arange(r1 - r0),
+                                       B.indptr[r0 + 1:r1 + 1] - B.indptr[r0:r1])
+        D = torch.zeros((r1 - r0, nh), dtype=torch.float64)
+        D[rows[keep], c[keep]] = B.data[a:b][keep].double()
+        yield r0, r1, D
+
+
+def _gram_layout(B: DeviceCSR, cm):
+    """csr_gram's input from a ``valued`` matrix: the kept entries packed by 64-wide
+    output-column tile, (tile, row) major, stored order within a row, as (tptr, local column
+    int32, value float64); tptr[t * n + r] is where row r of tile t starts.  Any injective
+    col_map, monotone or not.  O(nnz) memory (int32 temporaries) plus the n * tiles + 1
+    pointers; nothing n x nh."""
+    n, nh = B.shape
+    dev = B.device
+    oc = B.indices if cm is None else torch.index_select(cm, 0, B.indices)
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev),
+                                   B.indptr[1:] - B.indptr[:-1])
+    val = B.data
+    if cm is not None:
+        keep = oc >= 0
+        oc, rows, val = oc[keep], rows[keep], val[keep]
+        del keep
+    tile = oc >> 6
+    ntile = (nh + _GRAM_TILE - 1) // _GRAM_TILE
+    counts = torch.bincount(tile.long().mul_(n).add_(rows), minlength=ntile * n)
+    del rows
+    tptr = torch.zeros(ntile * n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=tptr[1:])
+    del counts
+    order = torch.sort(tile.to(torch.int16 if ntile < 32768 else torch.int32),
+                       stable=True).indices
+    del tile
+    lcol = (oc & (_GRAM_TILE - 1))[order].contiguous()
+    del oc
+    val = val[order].double().contiguous()
+    del order
+    return tptr, lcol, val
+
+
+def gram(A: DeviceCSR, *, value_dtype=torch.float64) -> torch.Tensor:
+    """T(A)^T T(A), (nh x nh) float64, of the view's transformed matrix with every value
+    rounded to ``value_dtype`` first -- without a dense copy.  Deterministic and bitwise
+    symmetric on the GPU (csr_gram: sparse outer products in LDS, no atomics)."""
+    n, nh = A.shape
+    dev = A.device
+    B = valued(A, value_dtype)
+    cm = _map(B.xf.get("col_map"), dev)
+    _check_injective(B, cm, nh, "gram")
+    if not use_native(B.data):
+        G = torch.zeros((nh, nh), dtype=torch.float64)
+        for _, _, D in _row_blocks(B, cm, 4096):
+            G += D.t() @ D
+        return G
+    _require_native()
+    if n == 0 or nh == 0:       # no launch: exact zeros
+        return torch.zeros((nh, nh), dtype=torch.float64, device=dev)
+    tptr, lcol, val = _gram_layout(B, cm)
+    S = int(_hip.csr_gram_slabs(n, nh))
+    part = torch.empty((S, nh, nh), dtype=torch.float64, device=dev)
+    _hip.csr_gram(tptr.data_ptr(), lcol.data_ptr(), val.data_ptr(), n, nh, part.data_ptr(),
+                  _stream_ptr(B.data))
+    return part.sum(dim=0)      # fixed-order reduction over the slabs
+
+
+def project(A: DeviceCSR, V: torch.Tensor, shift=None, *, value_dtype=torch.float64
+            ) -> torch.Tensor:
+    """T(A) @ V - shift for V (nh x c) -> (n x c) float64, the values rounded to
+    ``value_dtype`` first (the PCA scores with shift = mean @ V).  Fixed order, no atomics."""
+    n, nh = A.shape
+    dev = A.device
+    if V.dim() != 2 or V.shape[0] != nh:
+        raise ValueError(f"project: V has shape {tuple(V.shape)}, A has {nh} columns")
+    c = int(V.shape[1])
+    Vd = V.to(device=dev, dtype=torch.float64)
+    sh = _f64(shift, dev)
+    if sh is not None and tuple(sh.shape) != (c,):
+        raise ValueError(f"project: shift has shape {tuple(sh.shape)}, expected ({c},)")
+    B = valued(A, value_dtype)
+    cm = _map(B.xf.get("col_map"), dev)
+    _check_injective(B, cm, nh, "project")
+    if not use_native(B.data):
+        out = torch.zeros((n, c), dtype=torch.float64)
+        for r0, r1, D in _row_blocks(B, cm, 4096):
+            out[r0:r1] = D @ Vd
+        return out - sh if sh is not None else out
+    _require_native()
+    if n == 0 or nh == 0 or c == 0:     # no launch: exact zeros (less the shift)
+        out = torch.zeros((n, c), dtype=torch.float64, device=dev)
+        return out - sh if sh is not None else out
+    outs = []
+    for a in range(0, c, 64):   # the kernel takes <= 64 components: column blocks of V
+        Vb = Vd[:, a:a + 64].contiguous()
+        sb = sh[a:a + 64].contiguous() if sh is not None else None
+        ob = torch.empty((n, Vb.shape[1]), dtype=torch.float64, device=dev)
+        _hip.csr_project(B.indptr.data_ptr(), B.indices.data_ptr(), B.data.data_ptr(),
+                         int(B.data.dtype == torch.float64), n, nh, _ptr(cm), Vb.data_ptr(),
+                         int(Vb.shape[1]), _ptr(sb), ob.data_ptr(), _stream_ptr(B.data))
+        outs.append(ob)
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+
 def kth_nonneg(x: torch.Tensor, k: int) -> float:
     """The k-th smallest (0-based) of the non-negative entries of the float32 tensor x
     (negative entries are ignored), exactly: a 4-pass radix select over the IEEE bit

@@ -52,6 +52,11 @@ def _check_hvg_loess(hvg_loess):
         raise ValueError(f"hvg_loess must be 'direct' or 'native', not {hvg_loess!r}")
 
 
+def _check_pca_backend(pca_backend):
+    if pca_backend not in ("dense", "csr"):
+        raise ValueError(f"pca_backend must be 'dense' or 'csr', not {pca_backend!r}")
+
+
 def stdscale_quantile_celing(_adata, max_value=None, quantile_thresh=None):
     """Scale genes to unit variance (no centring), cap at ``max_value`` and at the
     global ``quantile_thresh`` quantile (preprocess.py:21-29).  The quantile is taken
@@ -145,11 +150,12 @@ class Preprocess:
                             n_top_rna_genes=2000, librarysize_targetsum=1e4,
                             max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
                             theta=1, save_output_base=None, max_iter_harmony=20, device=None,
-                            hvg_loess="direct"):
+                            hvg_loess="direct", pca_backend="dense"):
         """HVG-filtered, normalised, optionally Harmony-corrected input for cNMF plus a
         TP10K matrix (RNA [+ ADT]) for the tpm input (preprocess.py:135-247).
-        ``hvg_loess``: see :meth:`normalize_batchcorrect`."""
+        ``hvg_loess``, ``pca_backend``: see :meth:`normalize_batchcorrect`."""
         _check_hvg_loess(hvg_loess)
+        _check_pca_backend(pca_backend)
         if (not isinstance(_adata, Collection) or _is_anndata(_adata)) and feature_type_col is not None:
             ad = to_lite(_adata)
             is_adt = (ad.var[feature_type_col] == adt_feature_name).values
@@ -199,7 +205,7 @@ class Preprocess:
                 librarysize_targetsum=librarysize_targetsum, max_scaled_thresh=max_scaled_thresh,
                 quantile_thresh=quantile_thresh, theta=theta, makeplots=makeplots,
                 max_iter_harmony=max_iter_harmony, device=dev, _device_csr=dX,
-                hvg_loess=hvg_loess)
+                hvg_loess=hvg_loess, pca_backend=pca_backend)
         except BaseException:
             if tp_write is not None:
                 tp_write.exception()    # no write left running behind the error
@@ -227,7 +233,7 @@ class Preprocess:
                                n_top_genes=None, librarysize_targetsum=1e4,
                                max_scaled_thresh=None, quantile_thresh=.9999, theta=1,
                                makeplots=True, max_iter_harmony=20, device=None,
-                               _device_csr=None, hvg_loess="direct"):
+                               _device_csr=None, hvg_loess="direct", pca_backend="dense"):
         """Seurat-v3 HVGs, scaling + quantile ceiling, optional Harmony (preprocess.py:250-338).
 
         On a GPU with sparse counts and ``harmony_vars``, the counts are uploaded once and
@@ -236,8 +242,14 @@ class Preprocess:
         ``hvg_loess="direct"`` (default) fits the HVG mean-variance trend with
         ``pp.loess_fit`` as before, on the CPU with (genes x window) temporaries;
         ``"native"`` fits it with ``ops.loess`` in O(genes) memory on ``device``
-        (loess.hip on the GPU; docs/ARCHITECTURE.md "LOESS")."""
+        (loess.hip on the GPU; docs/ARCHITECTURE.md "LOESS").
+
+        ``pca_backend="dense"`` (default) runs the PCA ahead of Harmony on a dense copy of
+        the scaled TP10K matrix; ``"csr"`` computes the same PCA from the sparse counts
+        (``pp.pca_csr``: pca_csr.hip on the GPU; docs/ARCHITECTURE.md "Sparse PCA"), so
+        that no dense (cells x HVGs) matrix exists before the one Harmony corrects."""
         _check_hvg_loess(hvg_loess)
+        _check_pca_backend(pca_backend)
         ad = to_lite(_adata)
         dev = torch.device(device) if device is not None else _default_device()
         dX = _device_csr
@@ -253,7 +265,7 @@ class Preprocess:
         if harmony_vars is not None and dX is not None:
             ad = self._harmony_device(ad, dX, hv, normalize_librarysize, harmony_vars,
                                       librarysize_targetsum, max_scaled_thresh, quantile_thresh,
-                                      theta, makeplots, max_iter_harmony)
+                                      theta, makeplots, max_iter_harmony, pca_backend)
         elif harmony_vars is not None:
             anorm = pp.normalize_total(ad, target_sum=librarysize_targetsum, copy=True)
             anorm = anorm[:, hv]
@@ -264,7 +276,8 @@ class Preprocess:
                                            quantile_thresh=quantile_thresh)
             if makeplots:
                 make_count_hist(anorm, num_cells=1000)
-            pp.pca(anorm, use_highly_variable=False, zero_center=True, device=dev)
+            pp.pca(anorm, use_highly_variable=False, zero_center=True, device=dev,
+                   backend=pca_backend)
             sub.obsm["X_pca"] = anorm.obsm["X_pca"]
             src = sub if not normalize_librarysize else anorm
             Xd = src.X.toarray() if sp.issparse(src.X) else np.asarray(src.X)
@@ -284,14 +297,19 @@ class Preprocess:
         return ad, hvgs
 
     def _harmony_device(self, ad, A, hv, normalize_librarysize, harmony_vars, target_sum,
-                        max_scaled_thresh, quantile_thresh, theta, makeplots, max_iter_harmony):
+                        max_scaled_thresh, quantile_thresh, theta, makeplots, max_iter_harmony,
+                        pca_backend="dense"):
         """The harmony branch of normalize_batchcorrect (preprocess.py:300-324) with the
         counts resident on the GPU as CSR (ops.sparse): normalize_total, the HVG subset,
         scale(zero_center=False) with both ceilings and the densification are fused
         into column-statistics / densify kernel passes; PCA, Harmony and the MOE ridge
         correction consume the dense device matrices directly.  One D2H of the corrected
         matrix at the end.  The corrected X keeps the input's float dtype (the
-        reference's in-place ``Z_corr -= ...`` on the float32 matrix)."""
+        reference's in-place ``Z_corr -= ...`` on the float32 matrix).
+
+        ``pca_backend="csr"``: the PCA reads the scaled TP10K matrix as a view of the CSR
+        (``pp.pca_csr``); that matrix is densified only where it is also the one to correct
+        (``normalize_librarysize``), else just its first 1000 rows for the histogram."""
         from .models.harmony import moe_correct_expression
         from .ops import sparse as sops
         from .utils.anndata_lite import _take
@@ -307,8 +325,8 @@ class Preprocess:
         norm_dt = torch.float64 if f64 else torch.float32
         raw_dt = torch.float64 if (f64 or np.issubdtype(ad.X.dtype, np.integer)) else torch.float32
 
-        def scaled(row_scale, out_dtype):
-            # stdscale_quantile_celing of the (normalised) HVG subset, densified
+        def scaling(row_scale, out_dtype):
+            # stdscale_quantile_celing of the (normalised) HVG subset, as a transform
             xf = dict(row_scale=row_scale, col_map=cmap,
                       round_mid=row_scale is not None and out_dtype == torch.float32)
             _, var = sops.mean_var(A, ddof=1, n_out=nh, **xf)
@@ -322,12 +340,30 @@ class Preprocess:
                 if out_dtype == torch.float32:
                     thr = float(np.float32(thr))
                 mv = min(mv, thr)
-            return sops.densify(A, n_out=nh, col_div=std, max_value=mv, out_dtype=out_dtype, **xf)
+            return dict(xf, col_div=std, max_value=mv)
 
-        anorm = scaled(rs, norm_dt)
-        if makeplots:
-            make_count_hist(AnnData(X=anorm[:1000].cpu().numpy()), num_cells=1000)
-        X_pca = pp.pca_tensor(anorm, 50, zero_center=True)[0]
+        def scaled(row_scale, out_dtype, xf=None):
+            xf = scaling(row_scale, out_dtype) if xf is None else xf
+            return sops.densify(A, n_out=nh, out_dtype=out_dtype, **xf)
+
+        if pca_backend == "csr":
+            xf = scaling(rs, norm_dt)
+            X_pca = pp.pca_csr(A.view(n_out=nh, **xf), 50, zero_center=True,
+                               value_dtype=norm_dt)[0]
+            anorm = scaled(rs, norm_dt, xf) if normalize_librarysize else None
+            if makeplots and anorm is None:
+                m = min(n, 1000)     # the histogram's rows only: a CSR over indptr[:m + 1]
+                head = sops.DeviceCSR(A.indptr[:m + 1], A.indices, A.data, (m, A.shape[1]))
+                head = sops.densify(head, n_out=nh, out_dtype=norm_dt,
+                                    **dict(xf, row_scale=rs[:m]))
+                make_count_hist(AnnData(X=head.cpu().numpy()), num_cells=1000)
+            elif makeplots:
+                make_count_hist(AnnData(X=anorm[:1000].cpu().numpy()), num_cells=1000)
+        else:
+            anorm = scaled(rs, norm_dt)
+            if makeplots:
+                make_count_hist(AnnData(X=anorm[:1000].cpu().numpy()), num_cells=1000)
+            X_pca = pp.pca_tensor(anorm, 50, zero_center=True)[0]
         if normalize_librarysize:
             src = anorm
         else:

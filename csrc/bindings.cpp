@@ -454,6 +454,24 @@ PYBIND11_MODULE(_hip, m) {
                                b_f64, K, P<double>(part), reinterpret_cast<hipStream_t>(stream)),
                 "csr_tspmm");
         });
+  m.def("csr_gram_min_rows", []() { return cnmf_csr_gram_min_rows(); });
+  m.def("csr_gram_slabs", [](int n, int nh) { return cnmf_csr_gram_slabs(n, nh); });
+  m.def("csr_gram", [](uintptr_t tptr, uintptr_t lcol, uintptr_t val, int n, int nh,
+                       uintptr_t part, uintptr_t stream) {
+    check(cnmf_csr_gram(P<const long long>(tptr), P<const int>(lcol), P<const double>(val), n, nh,
+                        P<double>(part), reinterpret_cast<hipStream_t>(stream)),
+          "csr_gram");
+  });
+  m.def("csr_project",
+        [](uintptr_t indptr, uintptr_t indices, uintptr_t vals, int vals_f64, int n, int nh,
+           uintptr_t col_map, uintptr_t V, int ncomp, uintptr_t shift, uintptr_t out,
+           uintptr_t stream) {
+          check(cnmf_csr_project(P<const long long>(indptr), P<const int>(indices),
+                                 P<const void>(vals), vals_f64, n, nh, P<const int>(col_map),
+                                 P<const double>(V), ncomp, P<const double>(shift),
+                                 P<double>(out), reinterpret_cast<hipStream_t>(stream)),
+                "csr_project");
+        });
   m.def("radix_hist", [](uintptr_t x, long long m, unsigned prefix, unsigned mask, int shift,
                          uintptr_t hist, uintptr_t stream) {
     check(cnmf_radix_hist(P<const float>(x), m, prefix, mask, shift,

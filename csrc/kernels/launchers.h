@@ -224,6 +224,14 @@ hipError_t cnmf_csr_tspmm(const long long* indptr, const int* indices, const voi
                           hipStream_t stream);
 hipError_t cnmf_radix_hist(const float* x, long long m, unsigned int prefix, unsigned int mask,
                            int shift, unsigned long long* hist, hipStream_t stream);
+// sparse PCA (pca_csr.hip): Gram of a tile-packed CSR, scores from the stored CSR
+int cnmf_csr_gram_min_rows();
+int cnmf_csr_gram_slabs(int n, int nh);
+hipError_t cnmf_csr_gram(const long long* tptr, const int* lcol, const double* val, int n, int nh,
+                         double* part, hipStream_t stream);
+hipError_t cnmf_csr_project(const long long* indptr, const int* indices, const void* vals,
+                            int vals_f64, int n, int nh, const int* col_map, const double* V,
+                            int ncomp, const double* shift, double* out, hipStream_t stream);
 
 hipError_t cnmf_philox_fill(float* out, long long rows, long long cols, long long s_row,
                             long long s_col, long long rep_stride, long long row_offset,

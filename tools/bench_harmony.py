@@ -12,7 +12,8 @@ four categorical covariates, then times:
 2. cNMF prepare -> factorize (K=10, --n-iter replicates) -> combine -> consensus on the
    corrected matrix.
 
-Prints one JSON line with the stage wall-clocks.
+Prints one JSON line with the stage wall-clocks, the PCA step's own time and the peak device
+memory of the preprocess stage (``--pca-backend csr``: the PCA from the device CSR).
 """
 import argparse
 import json
@@ -83,6 +84,10 @@ def main():
     ap.add_argument("--n-iter", type=int, default=100)
     ap.add_argument("--max-iter-harmony", type=int, default=20,
                     help="the reference default (preprocess.py:138)")
+    ap.add_argument("--pca-backend", choices=["dense", "csr"], default="dense",
+                    help="PCA ahead of Harmony: on a dense copy (default) or from the device "
+                         "CSR (pca_csr.hip); the PCA step's time and the preprocess stage's "
+                         "peak device memory are reported either way")
     ap.add_argument("--gpu-busy", action="store_true",
                     help="also report GPU-busy seconds per stage (torch.profiler kernel time; "
                          "adds profiler overhead to the wall-clocks)")
@@ -123,6 +128,23 @@ def main():
     work = tempfile.mkdtemp(prefix="cnmf_harmony_")
     base = os.path.join(work, "hm")
     p = Preprocess(random_seed=0)
+    # the PCA step on its own clock (device work included), whichever backend runs it
+    from cnmf_torch_amd.models import pp
+    pca_s = []
+
+    def timed(fn):
+        def run(*args, **kw):
+            torch.cuda.synchronize() if torch.cuda.is_available() else None
+            t1 = time.perf_counter()
+            out = fn(*args, **kw)
+            torch.cuda.synchronize() if torch.cuda.is_available() else None
+            pca_s.append(time.perf_counter() - t1)
+            return out
+        return run
+
+    pp.pca_tensor, pp.pca_csr = timed(pp.pca_tensor), timed(pp.pca_csr)
+    if torch.cuda.is_available():
+        torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     prof = None
     if a.profile:
@@ -131,7 +153,8 @@ def main():
         prof.enable()
     corrected, tp10k, hvgs = staged("preprocess_harmony", lambda: p.preprocess_for_cnmf(
         ad, harmony_vars=["cov0", "cov1", "cov2", "cov3"], n_top_rna_genes=a.hvg,
-        makeplots=False, max_iter_harmony=a.max_iter_harmony, save_output_base=base))
+        makeplots=False, max_iter_harmony=a.max_iter_harmony, save_output_base=base,
+        pca_backend=a.pca_backend))
     if prof is not None:
         import io
         import pstats
@@ -142,6 +165,8 @@ def main():
             fh.write(buf.getvalue())
     torch.cuda.synchronize() if torch.cuda.is_available() else None
     t["preprocess_harmony"] = time.perf_counter() - t0
+    peak_gb = (round(torch.cuda.max_memory_allocated() / 1e9, 3)
+               if torch.cuda.is_available() else None)
     obj = cNMF(output_dir=work, name="hm_cnmf")
     t0 = time.perf_counter()
     staged("prepare", lambda: obj.prepare(
@@ -163,6 +188,8 @@ def main():
         "metric": "Harmony + cNMF end-to-end wall-clock", "unit": "s",
         "value": round(sum(v for k, v in t.items() if k != "simulate"), 2),
         "stages_s": {k: round(v, 2) for k, v in t.items()},
+        "pca_backend": a.pca_backend, "pca_s": round(sum(pca_s), 3),
+        "preprocess_peak_device_gb": peak_gb,
         "gpu_busy_s": busy or None,
         "harmony": getattr(p, "harmony_info_", None),
         "config": {"cells": a.cells, "genes": a.genes, "hvg": a.hvg, "covariates": 4,
